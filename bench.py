@@ -2,6 +2,12 @@
 """Throughput of the 3D VQ-VAE-2 training step (enc + VQ + dec, fwd + bwd + Adam) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3l_pub] [--eager] [--encode-only]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the result line; --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).  Everything
+that takes runs of its own beyond the K steps -- the kernel rooflines, the CPU baseline, the
+prior's attention-kernel timing -- is measured only with --full.
 
 N > 1 runs one process per GPU (RCCL); each rank trains on its own synthetic 512x512x128 volume
 (weak scaling: batch 1 per GPU, BASELINE.json configs[2]).  Started bare (`python bench.py --gpus
@@ -15,7 +21,7 @@ Rank 0 prints ONE JSON line.  Default workload = the BASELINE metric's configura
 --config 2l_pub is BASELINE configs[1] (256x256x128, batch 2); --encode-only is configs[3]
 (eval encode + codebook search per volume, the extract_embeddings.py path).
 
-The line carries:
+With --full the line also carries (--no-roofline / --no-cpu-baseline leave one of them out):
   roofline       the dominant kernel of the step -- the top kernel of the step's own rocprofv3
                  kernel-time ranking (profiles/rNN_step_top.json of the newest round, tools/step_profile.py) that has
                  a probe below -- launched alone on resident inputs and timed with HIP events on
@@ -73,8 +79,14 @@ def parse():
                    help="--encode-only: volumes per encode call (codes are per volume whatever the batch)")
     p.add_argument("--prior", action="store_true",
                    help="PixelSNAIL mid-level prior training step (configs[4]) instead of the VQ-VAE step")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-roofline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure what takes runs of its own: the kernel rooflines, "
+                        "the CPU baseline, --prior: the attention kernels alone")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (loss, updated parameters and buffers; "
+                        "--encode-only: the bottom level's codes) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    p.add_argument("--no-roofline", action="store_true", help="--full without the kernel rooflines")
     p.add_argument("--profile-steps", action="store_true", help="print per-step times to stderr")
     p.add_argument("--concurrent-wgrad", action="store_true",
                    help="run weight gradients on a side stream, overlapped with backward-data (measured "
@@ -547,6 +559,46 @@ def cpu_baseline(mkw, size, encode_only=False, sample=(256, 256, 64), reps=3):
                       f"({', '.join(f'{t:.2f}' for t in ts)} s), scaled by voxel count"}
 
 
+# ---------------------------------------------------------------------------------------------- outputs
+DUMP_BUDGET = 64 << 20  # bytes over all the arrays of one --dump-outputs
+
+
+def dump_outputs(dirname, named):
+    """--dump-outputs: write each (name, tensor) of `named` as DIR/<name>.npy, float32 (float64 for
+    64-bit values, so integer codes and counters stay exact).  When the arrays exceed DUMP_BUDGET in
+    total, every array larger than its equal share is cut to a fixed seeded sample of its elements:
+    the same indices in every run with the same arguments, so two builds compare element for element."""
+    import re
+
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    arrs = []
+    for name, t in named:
+        t = t.detach().to("cpu")
+        wide = t.dtype in (torch.float64, torch.int64)
+        arrs.append((re.sub(r"[^A-Za-z0-9_.-]", "_", name),
+                     t.to(torch.float64 if wide else torch.float32).contiguous().numpy()))
+    total = sum(v.nbytes for _, v in arrs)
+    share = DUMP_BUDGET // max(1, len(arrs))
+    for name, v in arrs:
+        if total > DUMP_BUDGET and v.nbytes > share:
+            pick = np.sort(np.random.default_rng(0).choice(v.size, share // v.itemsize, replace=False))
+            v = v.reshape(-1)[pick]
+        np.save(os.path.join(dirname, name + ".npy"), v)
+
+
+def model_outputs(model, loss):
+    """What a caller of the training step holds after it: the loss, the values the step logged,
+    the updated parameters (the flat fp32 master buffer) and the updated buffers (codebooks, EMA)."""
+    import torch
+    named = [("loss", loss)] if loss is not None else []
+    named += [("log." + k, v) for k, v in getattr(model, "logged", {}).items() if torch.is_tensor(v)]
+    named.append(("params", model.flat.data))
+    named += [("buffer." + n, b) for n, b in model.named_buffers()]
+    return named
+
+
 # ---------------------------------------------------------------------------------------------- main
 def capture(step, warmup):
     """Capture one call of step() as a HIP graph (after an allocator warm-up on the capture
@@ -599,6 +651,41 @@ def prior_cpu_baseline(sample=(8, 8, 8), reps=2):
                       f"median of {reps} after a warm-up ({t:.2f} s), scaled x{scale:.0f} by position count"}
 
 
+def prior_attention_timing(a, dev, dims, kw):
+    """--full: the prior's attention kernels alone, see the comment below."""
+    import torch
+
+    from vq3d import pixelsnail as PS
+    # the attention kernels alone (forward + backward of one stream at the step's shape), HIP
+    # events on the launching stream: flops = causal pairs x (fwd 2 (dk + dv) + bwd 2 (2 dk + 2 dv))
+    n, c, nh = dims[0] * dims[1] * dims[2], kw["model_dim"] // kw["bottleneck_divisor"], 8
+    dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    q, k, v = (torch.randn((1, c) + dims, device=dev).to(dtype).contiguous(memory_format=torch.channels_last_3d)
+               .requires_grad_(True) for _ in range(3))
+    gy = torch.randn((1, c) + dims, device=dev).to(dtype).contiguous(memory_format=torch.channels_last_3d)
+    for _ in range(3):
+        PS.CausalAttentionFn.apply(q, k, v, nh).backward(gy)
+    torch.cuda.synchronize()
+    st = torch.cuda.current_stream()
+    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+    reps = 10
+    e0.record(st)
+    for _ in range(reps):
+        y = PS.CausalAttentionFn.apply(q, k, v, nh)
+    e1.record(st)
+    for _ in range(reps):
+        y.backward(gy, retain_graph=True)
+    e2.record(st)
+    e2.synchronize()
+    tf, tb = e0.elapsed_time(e1) / reps, e1.elapsed_time(e2) / reps
+    d = c // nh
+    pairs = nh * n * (n + 1) / 2
+    return {"positions": n, "heads": nh, "head_dim": d, "fwd_ms": tf, "bwd_ms": tb,
+            "fwd_tflops": pairs * 4 * d / (tf * 1e-3) / 1e12,
+            "bwd_tflops": pairs * 8 * d / (tb * 1e-3) / 1e12,
+            "note": "matrix-core kernels (16-bit, head dim 8), fp32 online softmax; per stream and block (24 per step)"}
+
+
 def prior_main(a):
     import torch
 
@@ -607,6 +694,8 @@ def prior_main(a):
     from vq3d.optim import FusedAdam
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    import numpy as np
+    np.random.seed(0)  # the mixup draws come from numpy's global generator: the same lam in every run
     kw = {k: v for k, v in PRIOR.items() if k != "dims"}
     dims = PRIOR["dims"]
     model = PS.PixelSNAIL(PS.default_args(**kw), compute_dtype=a.dtype).to(dev)
@@ -646,30 +735,6 @@ def prior_main(a):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     ms = 1000.0 * elapsed / a.steps
-    # the attention kernels alone (forward + backward of one stream at the step's shape), HIP
-    # events on the launching stream: flops = causal pairs x (fwd 2 (dk + dv) + bwd 2 (2 dk + 2 dv))
-    n, c, nh = dims[0] * dims[1] * dims[2], kw["model_dim"] // kw["bottleneck_divisor"], 8
-    dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
-    q, k, v = (torch.randn((1, c) + dims, device=dev).to(dtype).contiguous(memory_format=torch.channels_last_3d)
-               .requires_grad_(True) for _ in range(3))
-    gy = torch.randn((1, c) + dims, device=dev).to(dtype).contiguous(memory_format=torch.channels_last_3d)
-    for _ in range(3):
-        PS.CausalAttentionFn.apply(q, k, v, nh).backward(gy)
-    torch.cuda.synchronize()
-    st = torch.cuda.current_stream()
-    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-    reps = 10
-    e0.record(st)
-    for _ in range(reps):
-        y = PS.CausalAttentionFn.apply(q, k, v, nh)
-    e1.record(st)
-    for _ in range(reps):
-        y.backward(gy, retain_graph=True)
-    e2.record(st)
-    e2.synchronize()
-    tf, tb = e0.elapsed_time(e1) / reps, e1.elapsed_time(e2) / reps
-    d = c // nh
-    pairs = nh * n * (n + 1) / 2
     res_line = {
         "metric": f"samples/sec (PixelSNAIL prior train step) on {dims[0]}x{dims[1]}x{dims[2]} codes",
         "value": 1000.0 / ms, "unit": "samples/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
@@ -680,12 +745,13 @@ def prior_main(a):
                    "model_dim": kw["model_dim"], "blocks_x_layers": [kw["num_blocks"], kw["num_layers_per_block"]],
                    "batch_per_gpu": 1, "global_batch": 1, "parallelism": "dp1", "final_loss": float(res.detach()),
                    "mixup_alpha": kw["mixup_alpha"]},
-        "attention_kernel": {"positions": n, "heads": nh, "head_dim": d, "fwd_ms": tf, "bwd_ms": tb,
-                             "fwd_tflops": pairs * 4 * d / (tf * 1e-3) / 1e12,
-                             "bwd_tflops": pairs * 8 * d / (tb * 1e-3) / 1e12,
-                             "note": "matrix-core kernels (16-bit, head dim 8), fp32 online softmax; per stream and block (24 per step)"},
     }
-    if not a.no_cpu_baseline:
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, [("loss", res), ("params", flat.data)] +
+                     [("buffer." + n, b) for n, b in model.named_buffers()])
+    if a.full:
+        res_line["attention_kernel"] = prior_attention_timing(a, dev, dims, kw)
+    if a.full and not a.no_cpu_baseline:
         print("[bench] prior CPU baseline", file=sys.stderr, flush=True)
         res_line["cpu_baseline"] = prior_cpu_baseline()
     print(json.dumps(res_line), flush=True)
@@ -755,6 +821,8 @@ def plumbing_main(a):
         step(i)
     elapsed, res, _ = timed_steps(step, a, world, dev)
     ok = abs(float(res[0]) - (world + 1) / 2.0) < 1e-6
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, [("buf", res)])
     if rank == 0:
         print(json.dumps({"metric": "launcher plumbing self-test (no model)", "value": world * a.steps / elapsed,
                           "unit": "steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -904,7 +972,13 @@ def main():
         # per-volume roofline / bytes times the volumes one step encodes (--encode-batch)
         res_line["step_conv_roofline_frac"] = ENC_ROOF_MS[a.config] * batch / ms
         res_line["encoder_traffic_frac"] = ENC_BYTES[a.config] * batch / (ms / 1e3) / 1e9 / HBM_PEAK_GBS
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.dump_outputs:
+        if a.encode_only:
+            # the encode step returns the bottom level's codes of its volumes
+            dump_outputs(a.dump_outputs, [("codes_level0", res)] if res is not None else [])
+        else:
+            dump_outputs(a.dump_outputs, model_outputs(model, res))
+    if rank == 0 and a.full and not a.no_roofline:
         def live(kind):
             """the kernel's average launch time inside one more (eager, untimed) step of this run"""
             if a.encode_only or world > 1:
@@ -924,7 +998,7 @@ def main():
             res_line["unprobed_above_dominant"] = unprobed
         if latency:
             res_line["latency_bound"] = latency
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         res_line["cpu_baseline"] = cpu_baseline(mkw, size, encode_only=a.encode_only)
     if rank == 0:
         print(json.dumps(res_line), flush=True)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Average duration of the dominant-kernel launches that bench.py's roofline measurement issues
-(the last N launches of the fused 18-channel block forward, bench.DOM), from a rocprofv3
+"""Average duration of the dominant-kernel launches that the roofline measurement of
+`bench.py --full` issues (the last N launches of the fused 18-channel block forward, bench.DOM), from a rocprofv3
 --kernel-trace CSV, to cross-check bench.py's HIP-event figure.
 
     python3 tools/dominant_from_trace.py gpurun_out/stats/run_kernel_trace.csv [N]

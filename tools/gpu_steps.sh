@@ -38,17 +38,17 @@ for s in "$@"; do
         file:*) run "file_$(basename "${s#file:}" .py)" 900 $PYT "${s#file:}" || exit $? ;;
         smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
         race) run race 600 python -u tools/dbg/lanes_race.py 3 4 || exit $? ;;
-        bench) run bench 600 python -u bench.py || exit $?
+        bench) run bench 600 python -u bench.py --full || exit $?
                tail -1 "gpurun_out/${TAG}_bench.log" > "gpurun_out/${TAG}_bench.json" ;;
-        eager) run eager 600 python -u bench.py --eager --no-cpu-baseline || exit $?
+        eager) run eager 600 python -u bench.py --eager --full --no-cpu-baseline || exit $?
                tail -1 "gpurun_out/${TAG}_eager.log" > "gpurun_out/${TAG}_eager.json" ;;
-        prior) run prior 600 python -u bench.py --prior || exit $?
+        prior) run prior 600 python -u bench.py --prior --full || exit $?
                tail -1 "gpurun_out/${TAG}_prior.log" > "gpurun_out/${TAG}_prior.json" ;;
-        cfg2) run cfg2 600 python -u bench.py --config 2l_pub || exit $?
+        cfg2) run cfg2 600 python -u bench.py --config 2l_pub --full || exit $?
               tail -1 "gpurun_out/${TAG}_cfg2.log" > "gpurun_out/${TAG}_cfg2.json" ;;
-        cfg4) run cfg4 600 python -u bench.py --encode-only || exit $?
+        cfg4) run cfg4 600 python -u bench.py --encode-only --full || exit $?
               tail -1 "gpurun_out/${TAG}_cfg4.log" > "gpurun_out/${TAG}_cfg4.json" ;;
-        cfg4b8) run cfg4b8 600 python -u bench.py --encode-only --encode-batch 8 || exit $?
+        cfg4b8) run cfg4b8 600 python -u bench.py --encode-only --encode-batch 8 --full || exit $?
                 tail -1 "gpurun_out/${TAG}_cfg4b8.log" > "gpurun_out/${TAG}_cfg4b8.json" ;;
         prof) rm -rf "gpurun_out/${TAG}_prof"
               run prof 600 rocprofv3 --kernel-trace --stats -d "gpurun_out/${TAG}_prof" -o run --output-format csv -- \
