@@ -317,16 +317,18 @@ __global__ __launch_bounds__(1024) void k_vq_ema_update(float *__restrict__ embe
 }
 
 // ---------------------------------------------------------------- first-pass init
-// two-pass mean / unbiased variance per dimension, fixed-order partials (fp64 accumulate)
+// two-pass mean / unbiased variance per dimension, fixed-order partials (fp64 accumulate).  The
+// second pass centres on the fp64 mean: centred on the fp32-rounded one the variance gains
+// (mean error / std)^2 relative, many fp32 ulp of std once |mean| >> std.
 template <typename TZ>
 __global__ __launch_bounds__(256) void k_vq_moments_part(const TZ *__restrict__ z, int64_t n, int d,
-                                                        int64_t rows_per_blk, const float *__restrict__ mean,
+                                                        int64_t rows_per_blk, const double *__restrict__ mean,
                                                         double *__restrict__ part) {
     __shared__ double red[4];
     const int64_t r0 = int64_t(blockIdx.x) * rows_per_blk;
     const int64_t r1 = min(n, r0 + rows_per_blk);
     for (int j = 0; j < d; ++j) {
-        const double mu = mean ? double(mean[j]) : 0.0;
+        const double mu = mean ? mean[j] : 0.0;
         double s = 0.0;
         for (int64_t r = r0 + threadIdx.x; r < r1; r += 256) {
             const double v = double(ld(z + r * d + j)) - mu;
@@ -338,12 +340,18 @@ __global__ __launch_bounds__(256) void k_vq_moments_part(const TZ *__restrict__ 
 }
 
 __global__ void k_vq_moments_fin(const double *__restrict__ part, int nb, int d, int64_t n, float *__restrict__ out,
-                                 int is_var) {
+                                 double *__restrict__ mean64, int is_var) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= d) return;
     double s = 0.0;
     for (int b = 0; b < nb; ++b) s += part[int64_t(b) * d + j];
-    out[j] = is_var ? float(sqrt(s / double(n - 1))) : float(s / double(n));
+    if (is_var) {
+        out[j] = float(sqrt(s / double(n - 1)));
+    } else {
+        const double m = s / double(n);
+        mean64[j] = m;
+        out[j] = float(m);
+    }
 }
 
 __global__ __launch_bounds__(256) void k_vq_init_apply(float *__restrict__ embed, float *__restrict__ embed_avg,
@@ -364,6 +372,8 @@ __global__ __launch_bounds__(256) void k_vq_init_apply(float *__restrict__ embed
 }
 
 // ---------------------------------------------------------------- host
+constexpr int kMomentBlocks = 1024;  // most row blocks of the moment partials
+
 struct VqPlan {
     int64_t nb_near, nb_stats;
     int nchunk, ck;  // codebook chunks of the split search (1: single pass)
@@ -383,10 +393,16 @@ static VqPlan plan_vq(int64_t n, int d, int k) {
     p.ck = k;
     if (p.nb_near < 128 && d <= 64) {
         int nc = int(std::min<int64_t>(std::max<int64_t>(1, 512 / p.nb_near), std::max(1, k / 8)));
+        if (nc > 1) {
+            // a chunk is staged in LDS whole: more chunks until ck * d fits the 64 KiB of the
+            // single pass (d <= 64 here, so a chunk always holds >= 256 codes)
+            const int ck_max = kLdsCodebookFloats / d;
+            nc = std::max(nc, (k + ck_max - 1) / ck_max);
+        }
         p.ck = (k + nc - 1) / nc;
         p.nchunk = (k + p.ck - 1) / p.ck;
     }
-    p.off_pb = p.off_mom + (size_t(1024) * d * 8 + 255) / 256 * 256;
+    p.off_pb = p.off_mom + (size_t(kMomentBlocks + 1) * d * 8 + 255) / 256 * 256;  // partials + fp64 mean
     p.off_pi = p.off_pb + (size_t(p.nchunk) * n * 4 + 255) / 256 * 256;
     p.bytes = p.off_pi + size_t(p.nchunk) * n * 4 + 256;
     return p;
@@ -533,12 +549,12 @@ int vq3d_vq_ema_stats(int32_t z_dtype, const void *z, int64_t n, int32_t d, cons
 }
 
 int vq3d_vq_ema_update(float *embed, float *embed_avg, float *cluster_size, const float *counts, const float *dw,
-                       int32_t k, int32_t d, float decay, float laplace_alpha, vq3d_stream_t stream) {
+                       int32_t k, int32_t d, double decay, float laplace_alpha, vq3d_stream_t stream) {
     if (k <= 0 || d <= 0) return fail("vq_ema_update: bad sizes");
     if (!embed || !embed_avg || !cluster_size || !counts || !dw) return fail("vq_ema_update: null pointer");
-    // torch: mul_(decay).add_(x, alpha=1-decay) with both scalars cast to fp32
-    const float omd = float(1.0 - double(decay));
-    k_vq_ema_update<<<1, 1024, 0, as_stream(stream)>>>(embed, embed_avg, cluster_size, counts, dw, k, d, decay, omd,
+    // torch: mul_(decay).add_(x, alpha=1-decay): 1 - decay in double, then both scalars cast to fp32
+    const float dec = float(decay), omd = float(1.0 - decay);
+    k_vq_ema_update<<<1, 1024, 0, as_stream(stream)>>>(embed, embed_avg, cluster_size, counts, dw, k, d, dec, omd,
                                                        laplace_alpha);
     return check_launch("vq_ema_update");
 }
@@ -550,16 +566,17 @@ int vq3d_vq_moments(int32_t z_dtype, const void *z, int64_t n, int32_t d, float 
     hipStream_t s = as_stream(stream);
     VqPlan p = plan_vq(n, d, 1);
     double *part = reinterpret_cast<double *>(static_cast<char *>(workspace) + p.off_mom);
-    const int64_t rpb = std::max<int64_t>(256, (n + 1023) / 1024);
+    double *mean64 = part + size_t(kMomentBlocks) * d;
+    const int64_t rpb = std::max<int64_t>(256, (n + kMomentBlocks - 1) / kMomentBlocks);
     const int nb = int((n + rpb - 1) / rpb);
     const unsigned fb = unsigned((d + 63) / 64);
     for (int pass = 0; pass < 2; ++pass) {
-        const float *mu = pass ? mean : nullptr;
+        const double *mu = pass ? mean64 : nullptr;
         if (z_dtype == VQ3D_F32)
             k_vq_moments_part<float><<<nb, 256, 0, s>>>((const float *)z, n, d, rpb, mu, part);
         else
             k_vq_moments_part<h16_t><<<nb, 256, 0, s>>>((const h16_t *)z, n, d, rpb, mu, part);
-        k_vq_moments_fin<<<fb, 64, 0, s>>>(part, nb, d, n, pass ? std : mean, pass);
+        k_vq_moments_fin<<<fb, 64, 0, s>>>(part, nb, d, n, pass ? std : mean, mean64, pass);
     }
     return check_launch("vq_moments");
 }

@@ -104,7 +104,7 @@ _SIGS = {
     "vq3d_vq_commit_loss": (c_int, [P, c_float, P, P]),
     "vq3d_vq_bwd": (c_int, [c_int, P, c_i64, c_int, P, P, c_int, P, P, c_float, P, P]),
     "vq3d_vq_ema_stats": (c_int, [c_int, P, c_i64, c_int, P, c_int, P, P, P, P]),
-    "vq3d_vq_ema_update": (c_int, [P, P, P, P, P, c_int, c_int, c_float, c_float, P]),
+    "vq3d_vq_ema_update": (c_int, [P, P, P, P, P, c_int, c_int, ctypes.c_double, c_float, P]),
     "vq3d_vq_moments": (c_int, [c_int, P, c_i64, c_int, P, P, P, P]),
     "vq3d_vq_init_apply": (c_int, [P, P, P, P, P, P, c_int, c_int, c_float, c_float, P]),
     "vq3d_parse_input_fwd": (c_int, [c_int, c_i64, c_int, P, P, P, P, P]),

@@ -397,9 +397,11 @@ int vq3d_vq_bwd(int32_t z_dtype, const void *z, int64_t n, int32_t d, const floa
 int vq3d_vq_ema_stats(int32_t z_dtype, const void *z, int64_t n, int32_t d, const int64_t *idx, int32_t k,
                       float *counts, float *dw, void *workspace, vq3d_stream_t stream);
 /* cluster_size = cs*decay + counts*(1-decay); embed_avg likewise with dw; Laplace smoothing;
- * embed = embed_avg / smoothed  (layers.py:649-663). counts/dw already world-summed. */
+ * embed = embed_avg / smoothed  (layers.py:649-663). counts/dw already world-summed.  decay is
+ * the module's double: torch rounds decay and (1 - decay) to fp32 separately, and the fp32
+ * rounding of 1 - decay cannot be recovered from an fp32 decay (0.99: 100 ulp apart). */
 int vq3d_vq_ema_update(float *embed, float *embed_avg, float *cluster_size, const float *counts,
-                       const float *dw, int32_t k, int32_t d, float decay, float laplace_alpha,
+                       const float *dw, int32_t k, int32_t d, double decay, float laplace_alpha,
                        vq3d_stream_t stream);
 /* mean[d] and unbiased std[d] over the n rows (layers.py:666-667) */
 int vq3d_vq_moments(int32_t z_dtype, const void *z, int64_t n, int32_t d, float *mean, float *std,
