@@ -42,6 +42,7 @@ using half_t = __bf16;
 constexpr int32_t VQ3D_HALF = VQ3D_BF16;
 #endif
 typedef half_t hx8 __attribute__((ext_vector_type(8)));  // one MFMA A / B fragment (8 elements)
+typedef float f32x4 __attribute__((ext_vector_type(4)));  // one 16x16 MFMA accumulator fragment
 #ifdef VQ3D_FP16
 #define VQ3D_MFMA_16X16X32 __builtin_amdgcn_mfma_f32_16x16x32_f16
 #else
@@ -71,6 +72,8 @@ __device__ __forceinline__ float ld(const h16_t *p) { return h2f_lo(*p); }
 // round-to-nearest-even f32 -> the 16-bit format (torch's conversion; NaN stays NaN): the hardware
 // v_cvt_pk_bf16_f32 / v_cvt_f16_f32 on gfx950
 __device__ __forceinline__ h16_t f2h(float f) { return __builtin_bit_cast(h16_t, static_cast<half_t>(f)); }
+// two values rounded to the 16-bit format in one dword: a in the low half, b in the high half
+__device__ __forceinline__ uint32_t pk2(float a, float b) { return uint32_t(f2h(a)) | (uint32_t(f2h(b)) << 16); }
 
 // n / d for 0 <= n < 2^31 without an integer divide (Granlund-Montgomery, host-built)
 struct FastDiv {
@@ -153,7 +156,7 @@ __device__ __forceinline__ void stvec(T *__restrict__ p, const float (&v)[N]) {
         r.w[0] = f2h(v[0]);
     } else {
 #pragma unroll
-        for (int i = 0; i < N / 2; ++i) r.w[i] = uint32_t(f2h(v[2 * i])) | (uint32_t(f2h(v[2 * i + 1])) << 16);
+        for (int i = 0; i < N / 2; ++i) r.w[i] = pk2(v[2 * i], v[2 * i + 1]);
     }
     if constexpr (B == 2) {
         *reinterpret_cast<uint16_t *>(p) = uint16_t(r.w[0]);

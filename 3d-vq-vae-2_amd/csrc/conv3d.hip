@@ -21,10 +21,9 @@
 #include "common.h"
 #include "conv_epi.h"
 #include "engines.h"
+#include "launch.h"
 
 #include <algorithm>
-#include <map>
-#include <utility>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>

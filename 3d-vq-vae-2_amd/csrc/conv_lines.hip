@@ -22,18 +22,15 @@
 // then per brick stages the lines, runs the MFMAs, parks the fp32 accumulators in LDS and
 // applies the fused epilogue with 16-byte loads / stores over the brick's contiguous D-runs.
 #include "engines.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
-#include <utility>
 
 namespace vq3d {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct LArgs {
     int B, Ca, Cb, C, N;      // GEMM-conv input channels (x then x2), output channels
@@ -121,10 +118,6 @@ __device__ __forceinline__ hx8 read8(const h16_t *base, int off) {
     return __builtin_bit_cast(hx8, r);
 }
 
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-    return uint32_t(f2h(lo)) | (uint32_t(f2h(hi)) << 16);
-}
-
 // copy VEC consecutive bf16 (prologue applied unless raw; zeros when !ok)
 template <int VEC>
 __device__ __forceinline__ void copy_unit(const h16_t *__restrict__ src, h16_t *dst, bool ok, const Prologue &pro,
@@ -137,7 +130,7 @@ __device__ __forceinline__ void copy_unit(const h16_t *__restrict__ src, h16_t *
                 uint32_t w4[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    w4[j] = pack2(pro.apply(h2f_lo(w4[j])), pro.apply(h2f_hi(w4[j])));
+                    w4[j] = pk2(pro.apply(h2f_lo(w4[j])), pro.apply(h2f_hi(w4[j])));
                 q = uint4{w4[0], w4[1], w4[2], w4[3]};
             }
         }
@@ -146,7 +139,7 @@ __device__ __forceinline__ void copy_unit(const h16_t *__restrict__ src, h16_t *
         uint32_t q = 0u;
         if (ok) {
             q = *reinterpret_cast<const uint32_t *>(src);
-            if (!raw) q = pack2(pro.apply(h2f_lo(q)), pro.apply(h2f_hi(q)));
+            if (!raw) q = pk2(pro.apply(h2f_lo(q)), pro.apply(h2f_hi(q)));
         }
         *reinterpret_cast<uint32_t *>(dst) = q;
     } else {
@@ -193,7 +186,7 @@ __device__ __forceinline__ uint4 pack_item(const LArgs &a, const float *__restri
                 ++kd;
             }
         }
-        pk[t / 2] = pack2(v2[0], v2[1]);
+        pk[t / 2] = pk2(v2[0], v2[1]);
     }
     return uint4{pk[0], pk[1], pk[2], pk[3]};
 }
@@ -449,7 +442,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NT == 1 ||
                         if (++co == a.N) co = 0;
                     }
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) o4[j] = pack2(v8[2 * j], v8[2 * j + 1]);
+                    for (int j = 0; j < 4; ++j) o4[j] = pk2(v8[2 * j], v8[2 * j + 1]);
                     *reinterpret_cast<uint4 *>(y + gaddr) = uint4{o4[0], o4[1], o4[2], o4[3]};
                 } else {
                     float x8[8], d8[8];
@@ -483,7 +476,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NT == 1 ||
                         v8[t] = val;
                     }
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) o4[j] = pack2(v8[2 * j], v8[2 * j + 1]);
+                    for (int j = 0; j < 4; ++j) o4[j] = pk2(v8[2 * j], v8[2 * j + 1]);
                     *reinterpret_cast<uint4 *>(y + gaddr) = uint4{o4[0], o4[1], o4[2], o4[3]};
                 }
             }
@@ -722,33 +715,6 @@ Plan plan_for(const vq3d_conv_desc *d, bool dgrad) {
                   d->kernel, 1, pp, circ, d->tap_mask, true);
 }
 
-// persistent grid: workgroups resident at the kernel's occupancy (per CU), bricks strided
-template <typename K>
-unsigned resident_blocks(K kernel, size_t lds, unsigned units) {
-    static std::map<std::pair<const void *, size_t>, int> cache;
-    const auto key = std::make_pair(reinterpret_cast<const void *>(kernel), lds);
-    int per_cu;
-    auto it = cache.find(key);
-    if (it != cache.end()) {
-        per_cu = it->second;
-    } else {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        (void)hipGetLastError();
-        cache[key] = per_cu;
-        if (std::getenv("VQ3D_VERBOSE")) std::fprintf(stderr, "[vq3d] lines occupancy %d blocks/CU at lds %zu\n", per_cu, lds);
-    }
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1)
-            n_cu = 256;
-        (void)hipGetLastError();
-    }
-    return std::max(1u, std::min(units, unsigned(per_cu * n_cu)));
-}
-
 template <bool DGRAD>
 void launch(const Plan &P, const h16_t *x, const h16_t *x2, const float *w, int wCt, const uint4 *wpk,
             const FwdEpi<h16_t> &fe,
@@ -757,14 +723,9 @@ void launch(const Plan &P, const h16_t *x, const h16_t *x2, const float *w, int 
 #define K(NT, ALN)                                                                                            \
     {                                                                                                         \
         auto kern = k_lines<NT, ALN, DGRAD>;                                                                  \
-        static bool attr = false;                                                                             \
-        if (!attr) {                                                                                          \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                   \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(kLdsMax));              \
-            (void)hipGetLastError();                                                                          \
-            attr = true;                                                                                      \
-        }                                                                                                     \
-        const unsigned nb = resident_blocks(kern, P.lds, unsigned(P.a.nbricks));                              \
+        opt_in_lds(kern, kLdsMax);                                                                            \
+        /* persistent grid: workgroups resident at the kernel's occupancy, bricks strided */                  \
+        const unsigned nb = resident_blocks(kern, 256, P.lds, unsigned(P.a.nbricks));                         \
         const dim3 grid{nb, unsigned(P.a.ntg), 1u};                                                           \
         const GridSum gs = grid_sum_for(s, int64_t(nb) * P.a.ntg, DGRAD && (dpre || dpost));                    \
         kern<<<grid, 256, P.lds, s>>>(P.a, x, x2, w, wCt, wpk, fe, be, gscale, y, y2, dpre, dpost, gs);       \

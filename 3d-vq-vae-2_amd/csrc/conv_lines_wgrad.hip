@@ -17,6 +17,7 @@
 // gradient with one atomic per entry (workgroups per column group are capped, so each address
 // sees a bounded number of adders).
 #include "engines.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -27,7 +28,6 @@ namespace vq3d {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void k_lines_wgrad(WArgs a, const h16_t *__res
                                 auto f = [&](uint32_t uu) {
                                     const float lo = pro.apply(h2f_lo(uu));
                                     const float hi = pro.apply(h2f_hi(uu));
-                                    return uint32_t(f2h(lo)) | (uint32_t(f2h(hi)) << 16);
+                                    return pk2(lo, hi);
                                 };
                                 qv = uint2{f(qv.x), f(qv.y)};
                             }
@@ -526,11 +526,6 @@ size_t lines_wgrad_workspace(const vq3d_conv_desc *d) {
     return P.ok ? size_t(P.nbx) * P.a.nent * 4 : 0;
 }
 
-namespace {
-
-
-}  // namespace
-
 bool lines_wgrad_applicable(const vq3d_conv_desc *d) { return plan_w(d).ok; }
 
 int launch_lines_wgrad(const vq3d_conv_desc *d, const void *x, const void *x2, const void *g, const float *pa,
@@ -547,13 +542,7 @@ int launch_lines_wgrad(const vq3d_conv_desc *d, const void *x, const void *x2, c
     auto run = [&](auto ntm_c, auto npw_c) {
         constexpr int NTM = decltype(ntm_c)::value, NPW = decltype(npw_c)::value;
         auto kern = k_lines_wgrad<NTM, NPW>;
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      int(kWLds));
-            (void)hipGetLastError();
-            attr = true;
-        }
+        opt_in_lds(kern, kWLds);
         kern<<<grid, 256, P.lds, s>>>(P.a, (const h16_t *)x, (const h16_t *)x2, (const h16_t *)g, part);
     };
     using I1 = std::integral_constant<int, 1>;

@@ -15,8 +15,6 @@
 // (included by conv3d.hip after the shared epilogue helpers)
 namespace vq3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct MArgs {
     int B, Ca, Cb, N;        // input channels (Ca from x, Cb from x2), output channels of this GEMM
     int iH, iW, iD;          // input grid of this GEMM
@@ -406,33 +404,6 @@ static MPlan plan_mfma(int B, int Ca, int Cb, int N, int iH, int iW, int iD, int
     return m;
 }
 
-// persistent grid: enough workgroups to fill every CU at the kernel's occupancy, bricks
-// strided over them (weights staged once per workgroup for single-chunk convs)
-template <typename K>
-static unsigned persistent_blocks(K kernel, size_t lds, unsigned units) {
-    static std::map<std::pair<const void *, size_t>, int> cache;  // occupancy per (kernel, LDS bytes)
-    const auto key = std::make_pair(reinterpret_cast<const void *>(kernel), lds);
-    auto it = cache.find(key);
-    int per_cu = 0;
-    if (it != cache.end()) {
-        per_cu = it->second;
-    } else {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        cache[key] = per_cu;
-    }
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1)
-            n_cu = 256;
-    }
-    static const bool verbose = std::getenv("VQ3D_VERBOSE") != nullptr;
-    if (verbose) std::fprintf(stderr, "[vq3d] persistent: occupancy %d blocks/CU, %d CUs, lds %zu\n", per_cu, n_cu, lds);
-    return std::max(1u, std::min(units, unsigned(per_cu * n_cu)));
-}
-
 template <bool DGRAD>
 static int launch_mfma(const MPlan &m, const h16_t *x, const h16_t *x2, const float *w, const FwdEpi<h16_t> &fe,
                        const BwdEpi<h16_t> &be, int cin_split, const float *gscale, h16_t *y, h16_t *y2,
@@ -441,7 +412,9 @@ static int launch_mfma(const MPlan &m, const h16_t *x, const h16_t *x2, const fl
 #define KL(CP, NT)                                                                                           \
     {                                                                                                        \
         auto kern = k_conv_mfma<CP, NT, DGRAD>;                                                              \
-        const unsigned nb = persistent_blocks(kern, m.lds, m.blocks);                                        \
+        /* persistent grid: the chip filled at the kernel's occupancy, bricks strided (weights */            \
+        /* staged once per workgroup for single-chunk convs) */                                              \
+        const unsigned nb = resident_blocks(kern, 256, m.lds, m.blocks);                                     \
         kern<<<nb, 256, m.lds, s>>>(m.a, x, x2, w, fe, be, cin_split, gscale, y, y2, dpre, dpost, nbricks,   \
                                     grid_sum_for(s, nb, DGRAD && (dpre || dpost)));                          \
     }

@@ -17,8 +17,6 @@ namespace vq3d {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct S2Args {
     int B, Cin1, Cin2, Cin, Cout;
     int iH, iW, iD, oH, oW, oD;
@@ -79,7 +77,7 @@ __device__ __forceinline__ void store_row(T *__restrict__ p, const float (&v)[N]
         for (int q = 0; q < N / 8; ++q) {
             uint32_t u[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) u[j] = uint32_t(f2h(v[8 * q + 2 * j])) | (uint32_t(f2h(v[8 * q + 2 * j + 1])) << 16);
+            for (int j = 0; j < 4; ++j) u[j] = pk2(v[8 * q + 2 * j], v[8 * q + 2 * j + 1]);
             reinterpret_cast<uint4 *>(p)[q] = uint4{u[0], u[1], u[2], u[3]};
         }
     } else {
@@ -186,7 +184,7 @@ __global__ __launch_bounds__(256) void k_dgrad_s2(S2Args a, const T *__restrict_
                 }
                 uint32_t qv[COT / 2];
 #pragma unroll
-                for (int j = 0; j < COT / 2; ++j) qv[j] = uint32_t(f2h(o[2 * j])) | (uint32_t(f2h(o[2 * j + 1])) << 16);
+                for (int j = 0; j < COT / 2; ++j) qv[j] = pk2(o[2 * j], o[2 * j + 1]);
                 if constexpr (COT == 4) *reinterpret_cast<uint2 *>(gx + v * COT) = uint2{qv[0], qv[1]};
                 else *reinterpret_cast<uint4 *>(gx + v * COT) = uint4{qv[0], qv[1], qv[2], qv[3]};
                 continue;
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(256) void k_dgrad_s2_cell(S2Args a, const h16_t *__
                 }
                 x2[h] = x;
             }
-            u[e2] = uint32_t(f2h(x2[0])) | (uint32_t(f2h(x2[1])) << 16);
+            u[e2] = pk2(x2[0], x2[1]);
         }
         afr[idx] = uint4{u[0], u[1], u[2], u[3]};
     }
@@ -368,8 +366,7 @@ __global__ __launch_bounds__(256) void k_dgrad_s2_cell(S2Args a, const h16_t *__
                 if (be.addend) val = val + ad[c];
                 o[c] = val;
             }
-            *reinterpret_cast<uint2 *>(gx + T.ev[m]) = uint2{uint32_t(f2h(o[0])) | (uint32_t(f2h(o[1])) << 16),
-                                                             uint32_t(f2h(o[2])) | (uint32_t(f2h(o[3])) << 16)};
+            *reinterpret_cast<uint2 *>(gx + T.ev[m]) = uint2{pk2(o[0], o[1]), pk2(o[2], o[3])};
         }
     };
     // each wave walks a contiguous range of tiles (consecutive 16-cell runs of the lines)
@@ -465,7 +462,7 @@ __global__ __launch_bounds__(256) void k_dgrad_s2_mma(S2Args a, const h16_t *__r
             const int64_t st_ = int64_t(a.Cin) * K3;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                u[e] = uint32_t(f2h(wp[(2 * e) * st_])) | (uint32_t(f2h(wp[(2 * e + 1) * st_])) << 16);
+                u[e] = pk2(wp[(2 * e) * st_], wp[(2 * e + 1) * st_]);
         }
         afr[idx] = uint4{u[0], u[1], u[2], u[3]};
     }
@@ -541,8 +538,7 @@ __global__ __launch_bounds__(256) void k_dgrad_s2_mma(S2Args a, const h16_t *__r
                 if (be.addend) val = val + add[c];
                 v[c] = val;
             }
-            *reinterpret_cast<uint2 *>(gx + o) = uint2{uint32_t(f2h(v[0])) | (uint32_t(f2h(v[1])) << 16),
-                                                       uint32_t(f2h(v[2])) | (uint32_t(f2h(v[3])) << 16)};
+            *reinterpret_cast<uint2 *>(gx + o) = uint2{pk2(v[0], v[1]), pk2(v[2], v[3])};
         }
     }
     if (dpre || dpost) {

@@ -19,8 +19,6 @@ namespace vq3d {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int VT = 32;  // voxels per tile
 constexpr int OT = 64;  // output channels per tile
 constexpr int CPT = 8;  // output channels per thread: OT / (256 / VT)

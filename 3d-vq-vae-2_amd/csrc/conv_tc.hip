@@ -75,7 +75,7 @@ __device__ __forceinline__ void vstore(T *__restrict__ p, const float (&v)[N]) {
             uint32_t w4[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                w4[j] = uint32_t(f2h(v[8 * q + 2 * j])) | (uint32_t(f2h(v[8 * q + 2 * j + 1])) << 16);
+                w4[j] = pk2(v[8 * q + 2 * j], v[8 * q + 2 * j + 1]);
             reinterpret_cast<uint4 *>(p)[q] = uint4{w4[0], w4[1], w4[2], w4[3]};
         }
     } else if constexpr (sizeof(T) == 4 && (N % 4) == 0) {

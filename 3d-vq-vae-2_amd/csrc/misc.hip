@@ -2,6 +2,7 @@
 // casts, and the error plumbing of libvq3d.
 #include "common.h"
 #include "engines.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -486,8 +487,7 @@ __device__ __forceinline__ void st4(float *p, const float v[4]) {
     *reinterpret_cast<float4 *>(p) = float4{v[0], v[1], v[2], v[3]};
 }
 __device__ __forceinline__ void st4(h16_t *p, const float v[4]) {
-    *reinterpret_cast<u32x2 *>(p) = u32x2{uint32_t(f2h(v[0])) | (uint32_t(f2h(v[1])) << 16),
-                                          uint32_t(f2h(v[2])) | (uint32_t(f2h(v[3])) << 16)};
+    *reinterpret_cast<u32x2 *>(p) = u32x2{pk2(v[0], v[1]), pk2(v[2], v[3])};
 }
 // the backward glue reductions 4 elements per thread-step on <= 512 workgroups (fewer partials
 // for the in-grid sum): n4 = n / 4
@@ -888,12 +888,7 @@ int vq3d_poison_lds(vq3d_stream_t stream) {
     // 64 KB per workgroup, 8 x the CU count of workgroups: every CU hosts at least two at once
     // over its whole run, so its 160 KB are overwritten in every placement the allocator uses
     constexpr int kBytes = 64 * 1024;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_poison_lds),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kBytes);
-        attr = true;
-    }
+    opt_in_lds(k_poison_lds, kBytes);
     k_poison_lds<<<256 * 8, 256, kBytes, as_stream(stream)>>>(kBytes / 16);
     return check_launch("poison_lds");
 }

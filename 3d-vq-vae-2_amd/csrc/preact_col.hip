@@ -34,7 +34,9 @@
 // accumulation; the W1 gradient reads u1 rounded to bf16 (the unfused wgrad's operand).  The
 // residual stream x / out (and g / gx) is stored bf16 or fp32 per tensor (template TX / TO): a run
 // of blocks keeps it fp32 between its blocks, as the reference's autocast blocks return fp32.
+#include "block_util.h"
 #include "engines.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -45,9 +47,6 @@
 #endif
 #ifndef COL_UNROLL_B
 #define COL_UNROLL_B 2  // ... and of the backward's phase B1
-#endif
-#ifndef COL_SWEIGHTS
-#define COL_SWEIGHTS 1  // the backward's W1 / W3 held in SGPRs (0: plain loads, for A/B timing)
 #endif
 #ifdef COL_PROBE  // phase clocks of k_col_bwd's first brick per workgroup (tools/probes/col_probe.hip)
 __device__ unsigned long long g_col_probe[4096][8];
@@ -64,24 +63,13 @@ __device__ unsigned long long g_col_probe[4096][8];
 #define CPROBE(k)
 #define CPROBE_DUMP
 #endif
-#ifndef COL_VSTENCIL
-#define COL_VSTENCIL 1  // (2, 1) backward: phase B as VALU stencils + an LDS-grouped reduction (0: MFMA, A/B)
-#endif
 #ifndef COL_NHB2
 #define COL_NHB2 2  // load batches of the (2, 1) backward's halo phase
-#endif
-#ifndef COL_PAIRS
-#define COL_PAIRS 1  // the backward's halo phase on position pairs (0: one position per item, A/B)
-#endif
-#ifndef FWD_PERSIST
-#define FWD_PERSIST 1  // the forward walks brick ranges too (its grid: CArgs::nwg)
 #endif
 
 namespace vq3d {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BH = 8, BW = 8, BD = 16, DV = 4;  // brick; voxels per thread along D
 constexpr int HL = BH + 2, WL = BW + 2, PL = BD + 2, NLN = HL * WL, HVX = NLN * PL;
@@ -116,14 +104,11 @@ constexpr int n_entries() {
 struct CArgs {
     int B, H, W, D;
     int nbh, nbw, nbd, nbricks;
-    int nwg;  // persistent backward grid (workgroups walking brick ranges; its partial rows)
-    int xcd;  // XCD-contiguous brick order (measured: faster up to 4096 bricks, slower at 32768)
+    int nwg;  // persistent grid (workgroups walking brick ranges; the backward's partial rows)
+    int xcd;  // XCD-contiguous order of a one-brick-per-workgroup grid (read by no kernel: both directions walk ranges)
 };
 
-__device__ __forceinline__ int wrapm(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
-__device__ __forceinline__ float bf(uint32_t u16) { return h2f_lo(u16); }
-__device__ __forceinline__ float rbf(float v) { return bf(f2h(v)); }
-__device__ __forceinline__ float elu_f(float z) { return z > 0.f ? z : __expf(z) - 1.f; }
+__device__ __forceinline__ float rbf(float v) { return h2f_lo(f2h(v)); }
 // N wave-uniform weights loaded once into SGPRs and laundered, so the compiler keeps them there: as
 // plain loads it re-issued them inside the halo / epilogue loops (32 s_load_dword per 4 halo items
 // of the (4, 2) backward, each with a lgkmcnt wait that also waited for the LDS stores)
@@ -134,38 +119,16 @@ struct SWeights {
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             float x = w[i];
-            if constexpr (COL_SWEIGHTS) asm volatile("" : "+s"(x));
+            asm volatile("" : "+s"(x));
             v[i] = x;
         }
     }
     __device__ __forceinline__ float operator[](int i) const { return v[i]; }
 };
-__device__ __forceinline__ float elu_d_act(float t, float b) {
-    const float z1 = t - b;
-    return z1 > 0.f ? 1.f : z1 + 1.f;
-}
-__device__ __forceinline__ f32x4 mfma(hx8 a, hx8 b, f32x4 c) {
-    return VQ3D_MFMA_16X16X32(a, b, c, 0, 0, 0);
-}
-// 8 consecutive bf16 from LDS at any element offset of a 4-byte aligned base
-__device__ __forceinline__ hx8 read8(const h16_t *base, int off) {
-    const uint32_t *q = reinterpret_cast<const uint32_t *>(base + (off & ~1));
-    const uint32_t sh = uint32_t(off & 1) * 2u;
-    const uint32_t u0 = q[0], u1 = q[1], u2 = q[2], u3 = q[3], u4 = q[4];
-    const uint4 r = {__builtin_amdgcn_alignbyte(u1, u0, sh), __builtin_amdgcn_alignbyte(u2, u1, sh),
-                     __builtin_amdgcn_alignbyte(u3, u2, sh), __builtin_amdgcn_alignbyte(u4, u3, sh)};
-    return __builtin_bit_cast(hx8, r);
-}
 // 8 bf16 at an even element offset (4-byte aligned)
 __device__ __forceinline__ hx8 read8e(const h16_t *p) {
     const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
     return __builtin_bit_cast(hx8, uint4{q[0], q[1], q[2], q[3]});
-}
-__device__ __forceinline__ hx8 pack8(const float (&v)[8]) {
-    uint32_t w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = uint32_t(f2h(v[2 * j])) | (uint32_t(f2h(v[2 * j + 1])) << 16);
-    return __builtin_bit_cast(hx8, uint4{w[0], w[1], w[2], w[3]});
 }
 
 // NW dwords (2, 4 or 8) to global memory as 8- / 16-byte stores
@@ -190,7 +153,7 @@ struct Vec {
 template <int N>
 __device__ __forceinline__ void unpack(const typename Vec<N>::U &u, float (&o)[N]) {
     if constexpr (N == 1) {
-        o[0] = bf(u);
+        o[0] = h2f_lo(u);
     } else if constexpr (N == 2) {
         o[0] = h2f_lo(u);
         o[1] = h2f_hi(u);
@@ -230,19 +193,12 @@ __device__ __forceinline__ typename Vec<N>::U packv(const float (&v)[N]) {
     } else {
         uint32_t w[(N + 1) / 2];
 #pragma unroll
-        for (int i = 0; i < N / 2; ++i) w[i] = uint32_t(f2h(v[2 * i])) | (uint32_t(f2h(v[2 * i + 1])) << 16);
+        for (int i = 0; i < N / 2; ++i) w[i] = pk2(v[2 * i], v[2 * i + 1]);
         if constexpr (N == 2) return w[0];
         else if constexpr (N == 4) return uint2{w[0], w[1]};
         else return uint4{w[0], w[1], w[2], w[3]};
     }
 }
-struct Scal {
-    float b1a, b1b, b2a, b2b, b3a, b3b, sc, b4;
-};
-__device__ __forceinline__ Scal load_scal(const vq3d_preact_params &p) {
-    return Scal{*p.bias1a, *p.bias1b, *p.bias2a, *p.bias2b, *p.bias3a, *p.bias3b, *p.scale, *p.bias4};
-}
-
 struct Org {
     int b, h0, w0, d0;
 };
@@ -270,10 +226,6 @@ __device__ __forceinline__ int halo_voxel(const CArgs &a, const Org &o, const in
     pos = q - line * PL;
     const int d = o.d0 - 1 + pos;
     return lbase[line] - o.d0 + (d < 0 ? d + a.D : (d >= a.D ? d - a.D : d));
-}
-__device__ __forceinline__ bool interior(int line, int pos) {
-    const int lh = line / WL, lw = line - lh * WL;
-    return lh >= 1 && lh <= BH && lw >= 1 && lw <= BW && pos >= 1 && pos <= BD;
 }
 
 // B fragment of k-step s of the row-windowed W2 (DGRAD: transposed, flipped taps)
@@ -333,13 +285,13 @@ template <int C, int BR>
 __device__ __forceinline__ void t2_of(const float (&xf)[C], const float *__restrict__ w1, const Scal &s, float (&t)[BR]) {
     float u[C];
 #pragma unroll
-    for (int c = 0; c < C; ++c) u[c] = elu_f(xf[c] + s.b1a) + s.b1b;
+    for (int c = 0; c < C; ++c) u[c] = elu_fast(xf[c] + s.b1a) + s.b1b;
 #pragma unroll
     for (int oo = 0; oo < BR; ++oo) {
         float acc = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) acc = fmaf(w1[oo * C + c], u[c], acc);
-        t[oo] = elu_f(acc + s.b2a) + s.b2b;
+        t[oo] = elu_fast(acc + s.b2a) + s.b2b;
     }
 }
 template <int C, int BR, typename TX, typename TO, int CH = 0>
@@ -359,7 +311,7 @@ __global__ __launch_bounds__(NT) void k_col_fwd(CArgs a, const TX *__restrict__ 
     Scal sn{};
     if constexpr ((CH & 2) != 0) sn = load_scal(pn);
     // one branch channel (BR = 1): phase B as a VALU stencil over the thread's own 4 voxels
-    constexpr bool VS = BR == 1 && COL_VSTENCIL;
+    constexpr bool VS = BR == 1;
     const SWeights<VS ? 27 : 1> w2s(w2);
     hx8 fw[K::KS];
 #pragma unroll
@@ -368,9 +320,9 @@ __global__ __launch_bounds__(NT) void k_col_fwd(CArgs a, const TX *__restrict__ 
     for (int i = tid; i < PADE; i += NT) t2h[HVX * BR + i] = 0;
     int woff[K::KS];
     win_offsets<BR>(row, kb, woff);
-    // persistent (FWD_PERSIST): the workgroup walks an XCD-contiguous brick range
-    const TileSched sc = FWD_PERSIST ? xcd_sched(a.nbricks)
-                                     : TileSched{a.xcd ? xcd_tile(a.nbricks) : int(blockIdx.x), a.nbricks, a.nbricks};
+    // persistent, as the backward: the workgroup walks an XCD-contiguous brick range (one brick per
+    // workgroup was the alternative)
+    const TileSched sc = xcd_sched(a.nbricks);
 #pragma unroll 1
     for (int brick = sc.t; brick < sc.end; brick += sc.step) {
         const Org o = brick_org(a, brick);
@@ -435,8 +387,8 @@ __global__ __launch_bounds__(NT) void k_col_fwd(CArgs a, const TX *__restrict__ 
 #pragma unroll
                 for (int k = 0; k < (DV + 2) / 2; ++k) {
                     const uint32_t tw = tp[k];
-                    tt[2 * k] = bf(tw & 0xffffu);
-                    tt[2 * k + 1] = bf(tw >> 16);
+                    tt[2 * k] = h2f_lo(tw & 0xffffu);
+                    tt[2 * k + 1] = h2f_lo(tw >> 16);
                 }
 #pragma unroll
                 for (int kd = 0; kd < 3; ++kd)
@@ -479,13 +431,13 @@ __global__ __launch_bounds__(NT) void k_col_fwd(CArgs a, const TX *__restrict__ 
         for (int i = 0; i < DV; ++i)
 #pragma unroll
             for (int oo = 0; oo < BR; ++oo)
-                t3v[i][oo] = rbf(elu_f((VS ? raw1[i] : accs[acc_at(v0 + i, BR) + oo]) + s.b3a) + s.b3b);
+                t3v[i][oo] = rbf(elu_fast((VS ? raw1[i] : accs[acc_at(v0 + i, BR) + oo]) + s.b3a) + s.b3b);
         {
             uint32_t w[DV * BR / 2];
 #pragma unroll
             for (int i = 0; i < DV * BR / 2; ++i) {
                 const int e0 = 2 * i, e1 = 2 * i + 1;
-                w[i] = uint32_t(f2h(t3v[e0 / BR][e0 % BR])) | (uint32_t(f2h(t3v[e1 / BR][e1 % BR])) << 16);
+                w[i] = pk2(t3v[e0 / BR][e0 % BR], t3v[e1 / BR][e1 % BR]);
             }
             if (t3o) store_words<DV * BR / 2>(t3o + vox0 * BR, w);  // NULL: eval forward, nothing saved
         }
@@ -513,7 +465,7 @@ __global__ __launch_bounds__(NT) void k_col_fwd(CArgs a, const TX *__restrict__ 
 #pragma unroll
             for (int i = 0; i < DV * BR / 2; ++i) {
                 const int e0 = 2 * i, e1 = 2 * i + 1;
-                w[i] = uint32_t(f2h(tn[e0 / BR][e0 % BR])) | (uint32_t(f2h(tn[e1 / BR][e1 % BR])) << 16);
+                w[i] = pk2(tn[e0 / BR][e0 % BR], tn[e1 / BR][e1 % BR]);
             }
             store_words<DV * BR / 2>(t2n + vox0 * BR, w);
         }
@@ -544,11 +496,11 @@ __global__ __launch_bounds__(NT) void k_col_bwd(CArgs a, const TO *__restrict__ 
     CPROBE(0)
     const Scal s = load_scal(p);
     const SWeights<C * BR> w3s(w3), w1s(w1);
-    const SWeights<(BR == 1 && COL_VSTENCIL) ? 27 : 1> w2s(w2);
+    const SWeights<BR == 1 ? 27 : 1> w2s(w2);
     hx8 fw[K::KS];
 #pragma unroll
     for (int k = 0; k < K::KS; ++k)
-        if constexpr (!(BR == 1 && COL_VSTENCIL)) fw[k] = w2_frag<BR, true>(w2, k, lane);  // MFMA path only
+        if constexpr (BR != 1) fw[k] = w2_frag<BR, true>(w2, k, lane);  // MFMA path only
     for (int i = tid; i < PADE; i += NT) z3h[HVX * BR + i] = 0;
     for (int i = tid; i < BR * NLN * (TP - PL) / 2; i += NT) {  // zero the channel-major line tails
         const int l = i / ((TP - PL) / 2), e = i - l * ((TP - PL) / 2);
@@ -563,8 +515,9 @@ __global__ __launch_bounds__(NT) void k_col_bwd(CArgs a, const TO *__restrict__ 
 #pragma unroll
         for (int c = 0; c < C; ++c) g3[oo][c] = dw1[oo][c] = 0.f;
     // one branch channel (BR = 1): phase B runs as VALU stencils over the thread's own 4 voxels
-    // (no MFMA: a single W2 row / column would use 1 / 16 of each), the W2 sums in 27 registers
-    constexpr bool VS = BR == 1 && COL_VSTENCIL;
+    // + an LDS-grouped reduction (no MFMA: a single W2 row / column would use 1 / 16 of each), the
+    // W2 sums in 27 registers
+    constexpr bool VS = BR == 1;
     float dw2[VS ? 27 : 1];
 #pragma unroll
     for (int i = 0; i < (VS ? 27 : 1); ++i) dw2[i] = 0.f;
@@ -589,10 +542,10 @@ __global__ __launch_bounds__(NT) void k_col_bwd(CArgs a, const TO *__restrict__ 
         __syncthreads();
         CPROBE(1)
         // A. gz3 on the halo; t2 on the halo (channel-major); interior sums and G3 = sum t3 (x) g.
-#if COL_PAIRS
-        // Work items are PAIRS of consecutive positions of a halo line (PL is even): one line /
-        // position computation per pair, and the channel-major t2 copy and the position-major gz3
-        // leave as whole-dword (pair) LDS stores instead of two 16-bit stores into one dword.
+        // Work items are PAIRS of consecutive positions of a halo line (PL is even; one position per
+        // item was the alternative): one line / position computation per pair, and the channel-major
+        // t2 copy and the position-major gz3 leave as whole-dword (pair) LDS stores instead of two
+        // 16-bit stores into one dword.
         // Two batches of pairs (COL_NHB2 = 1 for 2 channels measured no faster), every load of a
         // batch issued before its math.
         constexpr int NPAIR = HVX / 2, HP = PL / 2, NHB = C <= 2 ? COL_NHB2 : 2;
@@ -668,62 +621,6 @@ __global__ __launch_bounds__(NT) void k_col_bwd(CArgs a, const TO *__restrict__ 
                 }
             }
         }
-#else
-        // two batches of halo items: every load of a batch issued before its math (registers)
-        constexpr int PH = ((HVX + NT - 1) / NT + 1) / 2;
-#pragma unroll 1
-        for (int half = 0; half < 2; ++half) {
-            constexpr int P = PH;
-            Raw<TO, C> gv[P];
-            typename Vec<BR>::U tv3[P], tv2[P];
-#pragma unroll
-            for (int u = 0; u < P; ++u) {
-                int line, pos;
-                const int vx = halo_voxel(a, o, lbase, min(tid + (half * PH + u) * NT, HVX - 1), line, pos);
-                gv[u] = ldraw<TO, C>(g + int64_t(vx) * C);
-                tv3[u] = *reinterpret_cast<const typename Vec<BR>::U *>(t3 + int64_t(vx) * BR);
-                tv2[u] = *reinterpret_cast<const typename Vec<BR>::U *>(t2 + int64_t(vx) * BR);
-            }
-#pragma unroll
-            for (int u = 0; u < P; ++u) {
-                const int q = tid + (half * PH + u) * NT;
-                if (q < HVX) {
-                    const int line = q / PL, pos = q - line * PL;
-                    const bool in = interior(line, pos);
-                    float gf[C], t3f[BR], t2f[BR], z[BR];
-                    unraw<TO, C>(gv[u], gf);
-                    unpack<BR>(tv3[u], t3f);
-                    unpack<BR>(tv2[u], t2f);
-#pragma unroll
-                    for (int oo = 0; oo < BR; ++oo) {
-                        float acc = 0.f;
-#pragma unroll
-                        for (int c = 0; c < C; ++c) acc = fmaf(w3s[c * BR + oo], gf[c], acc);
-                        const float gt3 = s.sc * acc;
-                        z[oo] = gt3 * elu_d_act(t3f[oo], s.b3b);
-                        if (in) {
-                            s3b += gt3;
-                            s3a += z[oo];
-                            ssc = fmaf(acc, t3f[oo], ssc);
-#pragma unroll
-                            for (int c = 0; c < C; ++c) g3[oo][c] = fmaf(t3f[oo], gf[c], g3[oo][c]);
-                        }
-                        t2T[(oo * NLN + line) * TP + pos] = half_of<BR>(tv2[u], oo);  // the stored bits
-                    }
-                    const typename Vec<BR>::U zp = packv<BR>(z);
-                    *reinterpret_cast<typename Vec<BR>::U *>(z3h + q * BR) = zp;
-                    if (in) {
-#pragma unroll
-                        for (int c = 0; c < C; ++c) s4 += gf[c];
-                        const int lh = line / WL, lw = line - lh * WL;
-                        const int v = ((lh - 1) * BW + lw - 1) * BD + pos - 1;
-#pragma unroll
-                        for (int oo = 0; oo < BR; ++oo) z3T[oo * ZP + v] = f2h(z[oo]);
-                    }
-                }
-            }
-        }
-#endif
         __syncthreads();
         CPROBE(2)
         // the thread's 4 voxels (phase C): g and x in flight during phase B
@@ -749,7 +646,8 @@ __global__ __launch_bounds__(NT) void k_col_bwd(CArgs a, const TO *__restrict__ 
 #pragma unroll
             for (int t = 0; t < 27; ++t) wr[t] = rbf(w2s[26 - t]);
             const uint2 zq = *reinterpret_cast<const uint2 *>(z3T + ln * BD + d0);  // the 4 voxels' gz3
-            const float gz[DV] = {bf(zq.x & 0xffffu), bf(zq.x >> 16), bf(zq.y & 0xffffu), bf(zq.y >> 16)};
+            const float gz[DV] = {h2f_lo(zq.x & 0xffffu), h2f_lo(zq.x >> 16), h2f_lo(zq.y & 0xffffu),
+                                  h2f_lo(zq.y >> 16)};
 #pragma unroll
             for (int i = 0; i < DV; ++i) raw1[i] = 0.f;
 #pragma unroll
@@ -761,10 +659,10 @@ __global__ __launch_bounds__(NT) void k_col_bwd(CArgs a, const TO *__restrict__ 
 #pragma unroll
                 for (int k = 0; k < (DV + 2) / 2; ++k) {
                     const uint32_t zw = zp[k], tw = tp[k];
-                    zz[2 * k] = bf(zw & 0xffffu);
-                    zz[2 * k + 1] = bf(zw >> 16);
-                    tt[2 * k] = bf(tw & 0xffffu);
-                    tt[2 * k + 1] = bf(tw >> 16);
+                    zz[2 * k] = h2f_lo(zw & 0xffffu);
+                    zz[2 * k + 1] = h2f_lo(zw >> 16);
+                    tt[2 * k] = h2f_lo(tw & 0xffffu);
+                    tt[2 * k + 1] = h2f_lo(tw >> 16);
                 }
 #pragma unroll
                 for (int kd = 0; kd < 3; ++kd) {
@@ -834,7 +732,7 @@ __global__ __launch_bounds__(NT) void k_col_bwd(CArgs a, const TO *__restrict__ 
                     float gt2;
                     if constexpr (VS) gt2 = raw1[i];
                     else gt2 = accs[acc_at(v0 + i, BR) + oo];
-                    const float t2v = bf(t2T[(oo * NLN + hl0) * TP + dg * DV + i + 1]);
+                    const float t2v = h2f_lo(t2T[(oo * NLN + hl0) * TP + dg * DV + i + 1]);
                     const float zz = gt2 * elu_d_act(t2v, s.b2b);
                     s2b += gt2;
                     s2a += zz;
@@ -1021,7 +919,7 @@ template <int C, int BR>
 constexpr size_t bwd_lds() {
     const size_t tiles = size_t(HVX * BR + PADE + BR * NLN * TP + BR * ZP) * 2 + size_t(acc_floats(BR)) * 4 +
                          NLN * 4 + size_t(4 * n_entries<C, BR>()) * 4;
-    if (BR == 1 && COL_VSTENCIL)  // + room for the grouped partial-row reduction over the tiles
+    if (BR == 1)  // + room for the grouped partial-row reduction over the tiles
         return std::max(tiles, size_t((n_entries<C, BR>() + 3) / 4) * RPC * 16);
     return tiles;
 }
@@ -1053,12 +951,6 @@ CArgs make_args(int B, int H, int W, int D) {
     return a;
 }
 
-template <class Kern>
-void allow(Kern k, size_t lds) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    (void)hipGetLastError();
-}
-
 // the chain links of one forward launch (CH bits: 1 chained in, 2 chained out)
 struct FwdChain {
     int ch = 0;
@@ -1071,12 +963,8 @@ struct FwdChain {
 template <int C, int BR, typename TX, typename TO, int CH>
 void launch_fwd_ch(const CArgs &a, const void *x, const float *w1, const float *w2, const float *w3,
                    const vq3d_preact_params &p, void *out, h16_t *t2, h16_t *t3, const FwdChain &c, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        allow(k_col_fwd<C, BR, TX, TO, CH>, fwd_lds<C, BR>());
-        attr = true;
-    }
-    k_col_fwd<C, BR, TX, TO, CH><<<FWD_PERSIST ? a.nwg : a.nbricks, NT, fwd_lds<C, BR>(), s>>>(
+    opt_in_lds(k_col_fwd<C, BR, TX, TO, CH>, fwd_lds<C, BR>());
+    k_col_fwd<C, BR, TX, TO, CH><<<a.nwg, NT, fwd_lds<C, BR>(), s>>>(
         a, static_cast<const TX *>(x), w1, w2, w3, p, static_cast<TO *>(out), t2, t3, c.t2in, c.w1n, c.pn, c.t2n);
 }
 template <int C, int BR, typename TX, typename TO>
@@ -1093,11 +981,7 @@ template <int C, int BR, typename TX, typename TO>
 void launch_bwd(const CArgs &a, const void *g, const void *x, const h16_t *t2, const h16_t *t3, const float *w1,
                 const float *w2, const float *w3, const vq3d_preact_params &p, const vq3d_preact_grads &gr, float *part,
                 void *gx, int stages, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        allow(k_col_bwd<C, BR, TX, TO>, bwd_lds<C, BR>());
-        attr = true;
-    }
+    opt_in_lds(k_col_bwd<C, BR, TX, TO>, bwd_lds<C, BR>());
     if (stages & 1)
         k_col_bwd<C, BR, TX, TO><<<a.nwg, NT, bwd_lds<C, BR>(), s>>>(a, static_cast<const TO *>(g),
                                                                      static_cast<const TX *>(x), t2, t3, w1, w2, w3, p,

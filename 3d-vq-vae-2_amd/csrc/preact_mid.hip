@@ -31,7 +31,9 @@
 // so one v_mfma_f32_16x16x32_bf16 k-step covers a whole tap row: 9 k-steps per 16 voxels
 // instead of 14 with channel padding.  The five trailing elements of each window belong to the
 // next position and meet zero weights.
+#include "block_util.h"
 #include "engines.h"
+#include "launch.h"
 
 #include <cstdlib>
 
@@ -45,20 +47,11 @@
 #ifndef PM_BWD_PER
 #define PM_BWD_PER 0
 #endif
-// 1: the D16 tile kernels keep one run's epilogue at a time (a scheduling barrier between runs)
+// tiles of operands in flight ahead of k_pm_bwd2's current tile (1 or 2)
 #ifndef PM_DEPTH
-#define PM_DEPTH 1  // tiles of operands in flight ahead of k_pm_bwd2's current tile (1 or 2)
-#endif
-#ifndef PM_SB
-#define PM_SB 1
+#define PM_DEPTH 1
 #endif
 // minimum waves per SIMD the backward-data tile kernel is compiled for (2: at most 256 registers)
-#ifndef PM_FREG
-#define PM_FREG 1  // k_pm_bwd2: the 12 weight fragments in registers for the whole run (else one LDS read per use)
-#endif
-#ifndef PM_FREG_FWD
-#define PM_FREG_FWD 0  // k_pm_fwd likewise (it runs 3 workgroups per CU on 64 VGPRs)
-#endif
 #ifndef PM_BWD_WPE
 #define PM_BWD_WPE 2
 #endif
@@ -66,8 +59,6 @@
 namespace vq3d {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C = 18, BR = 9, TD = 8;  // block channels, branch channels, tile depth (one D-run)
 constexpr int NT = 256;                // threads per workgroup (every kernel)
@@ -102,35 +93,6 @@ struct Tile {
     static_assert(TV % 64 == 0 && NRUN % 4 == 0, "tile");
 };
 
-__device__ __forceinline__ int wrapm(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
-__device__ __forceinline__ float bf(uint32_t u16) { return h2f_lo(u16); }
-// ELU on the hardware exp (v_exp_f32 of z log2 e: ~1e-7 relative, far inside the bf16 rounding that
-// follows every use in the tile kernels; the libm expf is ~10 instructions)
-__device__ __forceinline__ float elu_fast(float z) { return z > 0.f ? z : __expf(z) - 1.f; }
-#ifndef PM_FAST_ELU
-#define PM_FAST_ELU 1  // the first block's t2 stage and the W1-gradient staging's u1 on elu_fast too (as k_pm_fwd's u1)
-#endif
-#if PM_FAST_ELU
-#define PM_ELU elu_fast
-#else
-#define PM_ELU elu
-#endif
-__device__ __forceinline__ float elu_d_act(float t, float b) {  // elu'(z) from t = elu(z) + b
-    const float z1 = t - b;
-    return z1 > 0.f ? 1.f : z1 + 1.f;
-}
-
-// 8 consecutive bf16 from LDS at element offset `off` (any parity; base 16-B aligned): five
-// dwords + v_alignbyte when odd
-__device__ __forceinline__ hx8 read8(const h16_t *base, int off) {
-    const uint32_t *q = reinterpret_cast<const uint32_t *>(base + (off & ~1));
-    const uint32_t sh = uint32_t(off & 1) * 2u;
-    const uint32_t u0 = q[0], u1 = q[1], u2 = q[2], u3 = q[3], u4 = q[4];
-    const uint4 r = {__builtin_amdgcn_alignbyte(u1, u0, sh), __builtin_amdgcn_alignbyte(u2, u1, sh),
-                     __builtin_amdgcn_alignbyte(u3, u2, sh), __builtin_amdgcn_alignbyte(u4, u3, sh)};
-    return __builtin_bit_cast(hx8, r);
-}
-
 // 8 bf16 at element offsets off + j * stride (j = 0..7) from LDS; zeros when !ok
 __device__ __forceinline__ hx8 gather8(const h16_t *base, int off, int stride, bool ok) {
     uint32_t w[4] = {0u, 0u, 0u, 0u};
@@ -140,17 +102,6 @@ __device__ __forceinline__ hx8 gather8(const h16_t *base, int off, int stride, b
             w[j] = uint32_t(base[off + 2 * j * stride]) | (uint32_t(base[off + (2 * j + 1) * stride]) << 16);
     }
     return __builtin_bit_cast(hx8, uint4{w[0], w[1], w[2], w[3]});
-}
-
-__device__ __forceinline__ hx8 pack8(const float (&v)[8]) {
-    uint32_t w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = uint32_t(f2h(v[2 * j])) | (uint32_t(f2h(v[2 * j + 1])) << 16);
-    return __builtin_bit_cast(hx8, uint4{w[0], w[1], w[2], w[3]});
-}
-
-__device__ __forceinline__ f32x4 mfma(hx8 a, hx8 b, f32x4 c) {
-    return VQ3D_MFMA_16X16X32(a, b, c, 0, 0, 0);
 }
 
 // copy n fp32 weights to LDS (coalesced; the fragments are then built from LDS instead of from
@@ -178,13 +129,6 @@ __device__ __forceinline__ hx8 w2_frag(const float *w2, int kk, int lane) {
         v[j] = x;
     }
     return pack8(v);
-}
-
-struct Scal {
-    float b1a, b1b, b2a, b2b, b3a, b3b, sc, b4;
-};
-__device__ __forceinline__ Scal load_scal(const vq3d_preact_params &p) {
-    return Scal{*p.bias1a, *p.bias1b, *p.bias2a, *p.bias2b, *p.bias3a, *p.bias3b, *p.scale, *p.bias4};
 }
 
 struct Org {
@@ -327,9 +271,10 @@ __global__ __launch_bounds__(NT) void k_pm_t2(int64_t nvox, const h16_t *__restr
                                               h16_t *__restrict__ t2o) {
     __shared__ float w1s[BR * C];
     // W1 and u1 rounded to bf16: the operands of the chained forward's matrix-core t2 stage
-    for (int i = threadIdx.x; i < BR * C; i += NT) w1s[i] = bf(f2h(w1[i]));
+    for (int i = threadIdx.x; i < BR * C; i += NT) w1s[i] = h2f_lo(f2h(w1[i]));
     __syncthreads();
     const Scal s = load_scal(p);
+    // elu_fast here and in the W1-gradient staging's u1, as in k_pm_fwd's u1 (the libm elu was the alternative)
     const int64_t npair = nvox / 2;
     for (int64_t q = int64_t(blockIdx.x) * NT + threadIdx.x; q < npair; q += int64_t(gridDim.x) * NT) {
         uint2 v[C / 2];
@@ -346,7 +291,7 @@ __global__ __launch_bounds__(NT) void k_pm_t2(int64_t nvox, const h16_t *__restr
                 const int e = h * C + c;  // element of the 36 bf16 of the pair
                 const uint2 w = v[e / 4];
                 const uint32_t d = (e & 2) ? w.y : w.x;
-                uu[c] = bf(f2h(PM_ELU(bf((e & 1) ? (d >> 16) : (d & 0xffffu)) + s.b1a) + s.b1b));
+                uu[c] = h2f_lo(f2h(elu_fast(h2f_lo((e & 1) ? (d >> 16) : (d & 0xffffu)) + s.b1a) + s.b1b));
             }
             float t2v[BR];
 #pragma unroll
@@ -355,7 +300,7 @@ __global__ __launch_bounds__(NT) void k_pm_t2(int64_t nvox, const h16_t *__restr
                 float acc = 0.f;
 #pragma unroll
                 for (int c = 0; c < C; ++c) acc = fmaf(w1s[o * C + c], uu[c], acc);
-                t2v[o] = PM_ELU(acc + s.b2a) + s.b2b;
+                t2v[o] = elu_fast(acc + s.b2a) + s.b2b;
             }
 #pragma unroll
             for (int o = 0; o < BR; ++o) {
@@ -387,7 +332,7 @@ __global__ __launch_bounds__(NT) void k_pm_bwd1(int64_t nvox, const h16_t *__res
     constexpr int NG = NT * C / 8, NTT = NT * BR / 8, PG = (NG + NT - 1) / NT, PT = (NTT + NT - 1) / NT;
     const int tid = threadIdx.x;
     // W3 rounded to bf16: the operand the chained stage of k_pm_bwd2 feeds the matrix cores
-    for (int i = tid; i < C * BR; i += NT) w3s[i] = bf(f2h(w3[i]));
+    for (int i = tid; i < C * BR; i += NT) w3s[i] = h2f_lo(f2h(w3[i]));
     const Scal s = load_scal(p);
     float s4 = 0.f, s3b = 0.f, s3a = 0.f, ssc = 0.f;
     const int64_t nblk = nvox / NT;
@@ -417,12 +362,12 @@ __global__ __launch_bounds__(NT) void k_pm_bwd1(int64_t nvox, const h16_t *__res
 #pragma unroll
             for (int j = 0; j < C / 2; ++j) {
                 const uint32_t q = gr[j];
-                gv[2 * j] = bf(q & 0xffffu);
-                gv[2 * j + 1] = bf(q >> 16);
+                gv[2 * j] = h2f_lo(q & 0xffffu);
+                gv[2 * j + 1] = h2f_lo(q >> 16);
                 s4 += gv[2 * j] + gv[2 * j + 1];
             }
 #pragma unroll
-            for (int o = 0; o < BR; ++o) tv[o] = bf(ts[tid * BR + o]);
+            for (int o = 0; o < BR; ++o) tv[o] = h2f_lo(ts[tid * BR + o]);
 #pragma unroll
             for (int o = 0; o < BR; ++o) {
                 float a3 = 0.f;
@@ -636,10 +581,10 @@ __device__ __forceinline__ void ex9(const Raw9 &r, uint32_t v, int kb, float (&o
     const bool hi = k == 2;
     const uint32_t lo = hi ? r.z : r.x, mid = hi ? 0u : r.y, top = hi ? 0u : r.z;
     const uint32_t p0 = __builtin_amdgcn_alignbyte(mid, lo, sub), p1 = __builtin_amdgcn_alignbyte(top, mid, sub);
-    o[0] = bf(p0 & 0xffffu);
-    o[1] = bf(p0 >> 16);
-    o[2] = bf(p1 & 0xffffu);
-    o[3] = bf(p1 >> 16);
+    o[0] = h2f_lo(p0 & 0xffffu);
+    o[1] = h2f_lo(p0 >> 16);
+    o[2] = h2f_lo(p1 & 0xffffu);
+    o[3] = h2f_lo(p1 >> 16);
 }
 // 18-channel rows (36 bytes, dword aligned): channels 4kb .. 4kb + 5 (one dwordx3; lane-group 3
 // uses all six: 12 .. 15 and 16, 17)
@@ -656,7 +601,6 @@ __device__ __forceinline__ Raw18 ld18(const h16_t *__restrict__ base, uint32_t v
 // pieces at a 36-byte stride, which the store path moves several times slower.  The image is
 // written and read by the same wave (LDS keeps a wave's accesses in order: no barrier).
 constexpr int QO9A = 16 * C, QO9B = QO9A + 16 * BR;  // element offsets of the 9-channel images
-__device__ __forceinline__ uint32_t pk2(float a, float b) { return uint32_t(f2h(a)) | (uint32_t(f2h(b)) << 16); }
 // channels 4kb .. 4kb + 3 of voxel n (lane-group 3 also 16, 17) of the 18-channel image
 __device__ __forceinline__ void put18(h16_t *st, int n, int kb, const float (&v)[6]) {
     uint32_t *p = reinterpret_cast<uint32_t *>(st + n * C + 4 * kb);  // 36 n + 8 kb bytes: dword aligned
@@ -746,17 +690,12 @@ __global__ __launch_bounds__(QNT) __attribute__((amdgpu_waves_per_eu(PM_BWD_WPE)
         frag[f * 64 + lane] = fr;
     }
     __syncthreads();  // the weights are read: the halo images' pads can be zeroed
-    // the A fragments in registers for the whole run (PM_FREG: 48 VGPRs; two waves per SIMD leave
-    // room) -- an LDS read per use put a ~100-cycle wait in front of every 1x1 stage's MFMA
-    hx8 fr[PM_FREG ? 12 : 1];
-    if constexpr (PM_FREG) {
+    // the A fragments in registers for the whole run (48 VGPRs; two waves per SIMD leave room) --
+    // an LDS read per use put a ~100-cycle wait in front of every 1x1 stage's MFMA
+    hx8 fr[12];
 #pragma unroll
-        for (int f = 0; f < 12; ++f) fr[f] = frag[f * 64 + lane];
-    }
-    auto wf = [&](int f, int l) -> hx8 {
-        if constexpr (PM_FREG) return fr[f];
-        else return frag[f * 64 + l];
-    };
+    for (int f = 0; f < 12; ++f) fr[f] = frag[f * 64 + lane];
+    auto wf = [&](int f, int) -> hx8 { return fr[f]; };
     zero_pads_q(img, 2);
     const Scal s = load_scal(p);
     Scal sp{};
@@ -848,7 +787,7 @@ __global__ __launch_bounds__(QNT) __attribute__((amdgpu_waves_per_eu(PM_BWD_WPE)
                 // zero, so acc, z, gt1 and the previous block's a3 are exactly 0 there (operands
                 // finite), adding nothing to the sums and meeting zero weights as K entries
                 const float z = acc[r][j] * elu_d_act(t2v[j], s.b2b);
-                z1[j] = bf(f2h(z));
+                z1[j] = h2f_lo(f2h(z));
                 s2b += acc[r][j];
                 s2a += z;
             }
@@ -859,10 +798,10 @@ __global__ __launch_bounds__(QNT) __attribute__((amdgpu_waves_per_eu(PM_BWD_WPE)
                 const f32x4 a0 = mfma(wf(9, ln), bz, f32x4{0.f, 0.f, 0.f, 0.f});
                 const f32x4 a1 = mfma(wf(10, ln), bz, f32x4{0.f, 0.f, 0.f, 0.f});
                 const Raw18 &xr = ex[r], &gr = eg[r];
-                const float xv[6] = {bf(xr.x & 0xffffu), bf(xr.x >> 16), bf(xr.y & 0xffffu), bf(xr.y >> 16),
-                                     bf(xr.z & 0xffffu), bf(xr.z >> 16)};
-                const float gv[6] = {bf(gr.x & 0xffffu), bf(gr.x >> 16), bf(gr.y & 0xffffu), bf(gr.y >> 16),
-                                     bf(gr.z & 0xffffu), bf(gr.z >> 16)};
+                const float xv[6] = {h2f_lo(xr.x & 0xffffu), h2f_lo(xr.x >> 16), h2f_lo(xr.y & 0xffffu),
+                                     h2f_lo(xr.y >> 16), h2f_lo(xr.z & 0xffffu), h2f_lo(xr.z >> 16)};
+                const float gv[6] = {h2f_lo(gr.x & 0xffffu), h2f_lo(gr.x >> 16), h2f_lo(gr.y & 0xffffu),
+                                     h2f_lo(gr.y >> 16), h2f_lo(gr.z & 0xffffu), h2f_lo(gr.z >> 16)};
                 const float gt1[6] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1]};
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
@@ -871,7 +810,7 @@ __global__ __launch_bounds__(QNT) __attribute__((amdgpu_waves_per_eu(PM_BWD_WPE)
                     const float ez = zx > 0.f ? 1.f : __expf(zx);
                     s1b += gt1[j];
                     s1a += gt1[j] * ez;
-                    gxv[j] = ok ? bf(f2h(gv[j] + gt1[j] * ez)) : 0.f;
+                    gxv[j] = ok ? h2f_lo(f2h(gv[j] + gt1[j] * ez)) : 0.f;
                     if constexpr (CHAIN) q4 += gxv[j];  // the previous block's g = this gx
                 }
             }
@@ -903,7 +842,7 @@ __global__ __launch_bounds__(QNT) __attribute__((amdgpu_waves_per_eu(PM_BWD_WPE)
             // the operands of the tile DEPTH steps ahead for this run (unconditional: on = this tile
             // at the end; a branch would keep the old values live)
             load_ep(et2, et3, ex, eg, ln, on, r);
-            if constexpr (PM_SB) __builtin_amdgcn_sched_barrier(0);  // one run's epilogue at a time (no interleaving)
+            __builtin_amdgcn_sched_barrier(0);  // one run's epilogue at a time (no interleaving)
         }
         return on;
     };
@@ -990,15 +929,9 @@ __global__ __launch_bounds__(QNT) __attribute__((amdgpu_waves_per_eu(PM_BWD_WPE)
         frag[f * 64 + lane] = fr;
     }
     __syncthreads();
-    hx8 fr[PM_FREG_FWD ? 12 : 1];  // as k_pm_bwd2 (PM_FREG_FWD)
-    if constexpr (PM_FREG_FWD) {
-#pragma unroll
-        for (int f = 0; f < 12; ++f) fr[f] = frag[f * 64 + lane];
-    }
-    auto wf = [&](int f, int l) -> hx8 {
-        if constexpr (PM_FREG_FWD) return fr[f];
-        else return frag[f * 64 + l];
-    };
+    // an LDS read per use: holding the 12 fragments in registers, as k_pm_bwd2 does, would cost the
+    // 3 workgroups per CU this kernel runs on 64 VGPRs
+    auto wf = [&](int f, int l) -> hx8 { return frag[f * 64 + l]; };
     zero_pads_q(img, 2);
     const Scal s = load_scal(p);
     Scal sn{};
@@ -1055,18 +988,19 @@ __global__ __launch_bounds__(QNT) __attribute__((amdgpu_waves_per_eu(PM_BWD_WPE)
             float t3v[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j)  // channels past 8 meet zero weights (finite: no masks)
-                t3v[j] = bf(f2h(elu_fast(acc[r][j] + s.b3a) + s.b3b));
+                t3v[j] = h2f_lo(f2h(elu_fast(acc[r][j] + s.b3a) + s.b3b));
             float ov[6];
             {
                 const hx8 bt = pack8({t3v[0], t3v[1], t3v[2], t3v[3], 0.f, 0.f, 0.f, 0.f});
                 const f32x4 a0 = mfma(wf(9, ln), bt, f32x4{0.f, 0.f, 0.f, 0.f});
                 const f32x4 a1 = mfma(wf(10, ln), bt, f32x4{0.f, 0.f, 0.f, 0.f});
                 const Raw18 &xr = ex[r];
-                const float xv[6] = {bf(xr.x & 0xffffu), bf(xr.x >> 16), bf(xr.y & 0xffffu), bf(xr.y >> 16),
-                                     bf(xr.z & 0xffffu), bf(xr.z >> 16)};
+                const float xv[6] = {h2f_lo(xr.x & 0xffffu), h2f_lo(xr.x >> 16), h2f_lo(xr.y & 0xffffu),
+                                     h2f_lo(xr.y >> 16), h2f_lo(xr.z & 0xffffu), h2f_lo(xr.z >> 16)};
                 const float o3[6] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1]};
 #pragma unroll
-                for (int j = 0; j < 6; ++j) ov[j] = bf(f2h(o3[j] * s.sc + s.b4 + xv[j]));  // j >= 4 used by kb 3 only
+                for (int j = 0; j < 6; ++j)  // j >= 4 used by kb 3 only
+                    ov[j] = h2f_lo(f2h(o3[j] * s.sc + s.b4 + xv[j]));
             }
             {
                 put18(st, nl, kl, ov);
@@ -1076,7 +1010,8 @@ __global__ __launch_bounds__(QNT) __attribute__((amdgpu_waves_per_eu(PM_BWD_WPE)
                 // the next block's u1 (k_pm_t2's rounding points) and t2
                 float u1[6];
 #pragma unroll
-                for (int j = 0; j < 6; ++j) u1[j] = bf(f2h(elu_fast(ov[j] + sn.b1a) + sn.b1b));  // zero-weight K past 17
+                for (int j = 0; j < 6; ++j)  // zero-weight K past 17
+                    u1[j] = h2f_lo(f2h(elu_fast(ov[j] + sn.b1a) + sn.b1b));
                 const hx8 bu = pack8({u1[0], u1[1], u1[2], u1[3], u1[4], u1[5], 0.f, 0.f});
                 const f32x4 a2 = mfma(wf(11, ln), bu, f32x4{0.f, 0.f, 0.f, 0.f});
                 float tn[4];
@@ -1087,7 +1022,7 @@ __global__ __launch_bounds__(QNT) __attribute__((amdgpu_waves_per_eu(PM_BWD_WPE)
             flush_run(st, ln, out + size_t(v0) * C, t3o ? t3o + size_t(v0) * BR : nullptr,
                           CHAIN ? t2n + size_t(v0) * BR : nullptr);
             ex[r] = ld18(x, run_vox0(on, r) + nl, kl);  // next tile's x (unconditional)
-            if constexpr (PM_SB) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
         o = on;
     }
@@ -1118,17 +1053,14 @@ constexpr int NT9 = 9 * 64;
 // channel stride CS has CS / 8 = 1 and the copy stride CK = 9 CS has CK / 8 = 9 (mod 16), so the 16
 // lanes of a lane group read 16 distinct 16-byte bank slots.  Copy 1 is the items' transpose;
 // copies 0 and 2 are built from it (dword reads + v_alignbyte once per row group, not per use).
-#ifndef PM_W2ROWS
-#define PM_W2ROWS 1  // D = 32: a wave per (tap row kh, chunk row), B fragments slid along the row (0: a wave per tap row)
-#endif
 template <int D>
 struct W2c {
-    // D = 32, 64 (PM_W2ROWS): 12 waves, wave (kh, r, s) sums taps (kh, 0..2) over chunk row r (line
+    // D = 32, 64 (ROWS): 12 waves, wave (kh, r, s) sums taps (kh, 0..2) over chunk row r (line
     // segment s of 32 voxels) -- its TW
     // lines' A fragments are read once for 3 taps and the B fragments of halo columns c, c + 1,
     // c + 2 are shared by neighbouring lines (TW + 2 column reads instead of 3 TW): 192 instead of
     // 432 16-byte LDS reads per chunk for the same 288 MFMAs.  Otherwise 9 waves, one per tap row.
-    static constexpr bool ROWS = PM_W2ROWS && (D == 32 || D == 64);
+    static constexpr bool ROWS = D == 32 || D == 64;
     static constexpr int SEG = D >= 32 ? D / 32 : 1;        // ROWS: 32-voxel k-steps per line
     static constexpr int NL = CHV / D;  // lines per chunk
     static constexpr int TH = NL >= 64 ? 8 : NL >= 16 ? 4 : NL >= 4 ? 2 : 1, TW = NL / TH;
@@ -1428,8 +1360,8 @@ __device__ __forceinline__ void pm_w13grad(int npb, const h16_t *__restrict__ gz
                     uint32_t w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        w[j] = uint32_t(f2h(PM_ELU(h2f_lo(w[j]) + s.b1a) + s.b1b)) |
-                               (uint32_t(f2h(PM_ELU(h2f_hi(w[j]) + s.b1a) + s.b1b)) << 16);
+                        w[j] = uint32_t(f2h(elu_fast(h2f_lo(w[j]) + s.b1a) + s.b1b)) |
+                               (uint32_t(f2h(elu_fast(h2f_hi(w[j]) + s.b1a) + s.b1b)) << 16);
                     q = u32x4{w[0], w[1], w[2], w[3]};
                 }
                 reinterpret_cast<u32x4 *>(raw)[i] = q;
@@ -1588,24 +1520,6 @@ constexpr size_t fwd_lds() { return size_t(2 * QIMG) * 2 + size_t(12 * 64) * 16 
 // images, 32 sums
 constexpr size_t bwd_lds() { return size_t(2 * QIMG) * 2 + size_t(12 * 64) * 16 + size_t(QNW * QSTG) * 2 + 32 * 4; }
 
-int n_cu() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-    }
-    return n;
-}
-
-template <class K>
-int resident(K kern, size_t lds, int threads = NT) {
-    int per = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, threads, lds) != hipSuccess || per < 1) per = 1;
-    (void)hipGetLastError();
-    return per;
-}
-
 PmArgs make_args(int B, int H, int W, int D, int TH, int TW) {
     PmArgs a;
     a.B = B;
@@ -1621,10 +1535,9 @@ PmArgs make_args(int B, int H, int W, int D, int TH, int TW) {
 
 // resident workgroups per CU of a tile kernel (dynamic LDS opted in once)
 template <class K>
-int per_cu(K kern, size_t lds, int threads = NT) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              int(lds));
-    return resident(kern, lds, threads);
+int per_cu(K kern, size_t lds, int threads) {
+    opt_in_lds(kern, lds);
+    return resident_per_cu(kern, threads, lds);
 }
 // K2 grid: both variants must give the same count (the chained variant writes the previous
 // block's K1 partial rows, whose count the reduction assumes to be the K2 grid)
@@ -1641,13 +1554,15 @@ constexpr size_t w13_lds() { return size_t(96 * SP + W13_RAW) * 2; }  // + the r
 
 template <int D>
 void launch_w2(const PmArgs &a, int nwa, int npc, const h16_t *gz3, const h16_t *t2, float *p2a, hipStream_t s) {
-    static bool init = false;
-    if (!init) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_pm_w2grad<D>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(W2c<D>::LDS));
-        init = true;
-    }
+    opt_in_lds(k_pm_w2grad<D>, W2c<D>::LDS);
     k_pm_w2grad<D><<<nwa, W2c<D>::NTW, W2c<D>::LDS, s>>>(a, int(int64_t(a.B) * a.H * a.W * a.D / CHV), npc, gz3, t2, p2a);
+}
+
+template <int D>
+void launch_w2_run(dim3 grid, const PmArgs &a, int nchunk, int npc, const MidRunWs &wr, const MidRunPtrs &r,
+                   hipStream_t s) {
+    opt_in_lds(k_pm_w2grad_run<D>, W2c<D>::LDS);
+    k_pm_w2grad_run<D><<<grid, W2c<D>::NTW, W2c<D>::LDS, s>>>(a, nchunk, npc, wr, r);
 }
 
 void launch_fwd(int batch, int h, int w, int dd, const void *x, const float *w2, const float *w3,
@@ -1880,15 +1795,6 @@ int vq3d_preact_mid_wgrad_run(int32_t dtype, int32_t nblocks, int32_t batch, int
     const PmArgs a = make_args(batch, h, w, dd, BTH, BTW);
     const int nchunk = int(int64_t(batch) * h * w * dd / CHV);
     auto off = [&](const void *p) { return int64_t(static_cast<const char *>(p) - b0); };
-    static bool init = false;
-    if (!init) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_pm_w2grad_run<8>), hipFuncAttributeMaxDynamicSharedMemorySize, int(W2c<8>::LDS));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_pm_w2grad_run<16>), hipFuncAttributeMaxDynamicSharedMemorySize, int(W2c<16>::LDS));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_pm_w2grad_run<32>), hipFuncAttributeMaxDynamicSharedMemorySize, int(W2c<32>::LDS));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_pm_w2grad_run<64>), hipFuncAttributeMaxDynamicSharedMemorySize, int(W2c<64>::LDS));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_pm_w2grad_run<128>), hipFuncAttributeMaxDynamicSharedMemorySize, int(W2c<128>::LDS));
-        init = true;
-    }
     for (int i0 = 0; i0 < nblocks; i0 += MAXRUN) {  // MAXRUN blocks per launch (kernel-argument tables)
         const int nb = std::min(MAXRUN, nblocks - i0);
         MidRunPtrs r{};
@@ -1901,11 +1807,11 @@ int vq3d_preact_mid_wgrad_run(int32_t dtype, int32_t nblocks, int32_t batch, int
         MidRunWs wr{b0 + size_t(i0) * workspace_stride, workspace_stride, off(m.gz3), off(m.gz1), off(m.p2a), off(m.p2b)};
         const dim3 ga(unsigned(m.nwa), unsigned(nb));
         switch (dd) {
-            case 8: k_pm_w2grad_run<8><<<ga, W2c<8>::NTW, W2c<8>::LDS, s>>>(a, nchunk, m.npc, wr, r); break;
-            case 16: k_pm_w2grad_run<16><<<ga, W2c<16>::NTW, W2c<16>::LDS, s>>>(a, nchunk, m.npc, wr, r); break;
-            case 32: k_pm_w2grad_run<32><<<ga, W2c<32>::NTW, W2c<32>::LDS, s>>>(a, nchunk, m.npc, wr, r); break;
-            case 64: k_pm_w2grad_run<64><<<ga, W2c<64>::NTW, W2c<64>::LDS, s>>>(a, nchunk, m.npc, wr, r); break;
-            default: k_pm_w2grad_run<128><<<ga, W2c<128>::NTW, W2c<128>::LDS, s>>>(a, nchunk, m.npc, wr, r); break;
+            case 8: launch_w2_run<8>(ga, a, nchunk, m.npc, wr, r, s); break;
+            case 16: launch_w2_run<16>(ga, a, nchunk, m.npc, wr, r, s); break;
+            case 32: launch_w2_run<32>(ga, a, nchunk, m.npc, wr, r, s); break;
+            case 64: launch_w2_run<64>(ga, a, nchunk, m.npc, wr, r, s); break;
+            default: launch_w2_run<128>(ga, a, nchunk, m.npc, wr, r, s); break;
         }
         k_pm_w13grad_run<<<dim3(unsigned(m.nchb), unsigned(nb)), NT, w13_lds(), s>>>(m.npb, wr, r, params + size_t(i0) * 11);
     }

@@ -20,7 +20,9 @@
 //   (W3: sum g t3, W2: sum gz3 t2(shifted), W1: sum gz1 u1) and the eight scalar-gradient
 //   partials go to the workspace [entry][brick]; a second launch sums every entry over the
 //   bricks in a fixed order (deterministic, one adder per gradient entry).
+#include "block_util.h"
 #include "engines.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -47,12 +49,6 @@ __device__ unsigned long long g_small_probe[1024][12];  // and stored at the end
 #define SPROBE(k)
 #define SPROBE_DUMP
 #endif
-#ifndef SMALL_TSPLIT
-#define SMALL_TSPLIT 1  // bricks below NT voxels: the 27 taps over NT / nvb thread groups (0: one voxel per thread)
-#endif
-#ifndef SMALL_BPRE
-#define SMALL_BPRE 1  // backward prologue: 0 weights staged first, 1 + halo loads before, 2 + the voxel x too
-#endif
 #ifndef SMALL_TU
 #define SMALL_TU 1  // unroll of the per-voxel tap loops (timing experiments)
 #endif
@@ -74,23 +70,10 @@ constexpr int n_entries(int C, int BR) { return C * BR + 27 * BR * BR + BR * C; 
 #endif
 constexpr int s2_of(int BR) { return BR >= 4 ? SMALL_S2 : 28; }  // W2-gradient sub-streams (9 each)
 
-__device__ __forceinline__ int wrapm(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
 __device__ __forceinline__ float rbf(float v) { return h2f_lo(uint32_t(f2h(v))); }
-#ifndef SMALL_FASTEXP
-#define SMALL_FASTEXP 1  // the brick kernels' elu on the hardware exp (v_exp_f32), as the column kernels' elu_f
-#endif
-__device__ __forceinline__ float belu(float z) {
-    if constexpr (SMALL_FASTEXP) return z > 0.f ? z : __expf(z) - 1.f;
-    else return elu(z);
-}
-__device__ __forceinline__ float belu_grad(float z) {
-    if constexpr (SMALL_FASTEXP) return z > 0.f ? 1.f : __expf(z);
-    else return elu_grad(z);
-}
-__device__ __forceinline__ float elu_d_act(float t, float b) {  // elu'(z) from t = elu(z) + b
-    const float z1 = t - b;
-    return z1 > 0.f ? 1.f : z1 + 1.f;
-}
+// the brick kernels' elu is elu_fast, as the column kernels' (the libm elu / elu_grad were the
+// alternative); its derivative on the hardware exp likewise
+__device__ __forceinline__ float belu_grad(float z) { return z > 0.f ? 1.f : __expf(z); }
 
 // N consecutive bf16 (N in 1, 2, 4, 8; the address is N * 2-byte aligned) <-> fp32 registers
 template <int N>
@@ -128,7 +111,7 @@ __device__ __forceinline__ void stv(h16_t *__restrict__ p, const float (&v)[N]) 
     } else {
         uint32_t w[N / 2];
 #pragma unroll
-        for (int i = 0; i < N / 2; ++i) w[i] = uint32_t(f2h(v[2 * i])) | (uint32_t(f2h(v[2 * i + 1])) << 16);
+        for (int i = 0; i < N / 2; ++i) w[i] = pk2(v[2 * i], v[2 * i + 1]);
         if constexpr (N == 2) *reinterpret_cast<uint32_t *>(p) = w[0];
         else if constexpr (N == 4) *reinterpret_cast<uint2 *>(p) = uint2{w[0], w[1]};
         else *reinterpret_cast<uint4 *>(p) = uint4{w[0], w[1], w[2], w[3]};
@@ -176,13 +159,6 @@ __device__ __forceinline__ int64_t halo_vox(const SArgs &a, const Brick &k, int 
 __device__ __forceinline__ int tap_off(const SArgs &a, int tap) {
     const int kd = tap % 3, kw = (tap / 3) % 3, kh = tap / 9;
     return ((kh - 1) * a.hw + kw - 1) * a.hd + kd - 1;
-}
-
-struct Scal {
-    float b1a, b1b, b2a, b2b, b3a, b3b, sc, b4;
-};
-__device__ __forceinline__ Scal load_scal(const vq3d_preact_params &p) {
-    return Scal{*p.bias1a, *p.bias1b, *p.bias2a, *p.bias2b, *p.bias3a, *p.bias3b, *p.scale, *p.bias4};
 }
 
 // A workgroup's weights staged through registers: loaded (clamped, unconditional) before the
@@ -260,14 +236,14 @@ __global__ __launch_bounds__(NT) void k_small_fwd(SArgs a, const TX *__restrict_
                 float xv[C];
                 unraw<TX, C>(xr[u], xv);
 #pragma unroll
-                for (int c = 0; c < C; ++c) xv[c] = belu(xv[c] + s.b1a) + s.b1b;
+                for (int c = 0; c < C; ++c) xv[c] = elu_fast(xv[c] + s.b1a) + s.b1b;
                 float t[BR];
 #pragma unroll
                 for (int o = 0; o < BR; ++o) {
                     float acc = 0.f;
 #pragma unroll
                     for (int c = 0; c < C; ++c) acc = fmaf(w1s[o * C + c], xv[c], acc);
-                    t[o] = rbf(belu(acc + s.b2a) + s.b2b);
+                    t[o] = rbf(elu_fast(acc + s.b2a) + s.b2b);
                     t2h[q * BR + o] = t[o];
                 }
                 if (vi[u] >= 0 && t2o) stv<BR>(t2o + vox[u] * BR, t);
@@ -281,7 +257,7 @@ __global__ __launch_bounds__(NT) void k_small_fwd(SArgs a, const TX *__restrict_
             const int64_t vox = brick_vox(a, k, v);
             float t3v[BR], ov[C];
 #pragma unroll
-            for (int o = 0; o < BR; ++o) t3v[o] = rbf(belu(acc[o] + s.b3a) + s.b3b);
+            for (int o = 0; o < BR; ++o) t3v[o] = rbf(elu_fast(acc[o] + s.b3a) + s.b3b);
             if (t3o) stv<BR>(t3o + vox * BR, t3v);
 #pragma unroll
             for (int co = 0; co < C; ++co) {
@@ -307,7 +283,9 @@ __global__ __launch_bounds__(NT) void k_small_fwd(SArgs a, const TX *__restrict_
                 }
             }
         };
-        if (SMALL_TSPLIT && a.nvb < NT) {
+        // bricks below NT voxels: the 27 taps over NT / nvb thread groups (one voxel per thread, the
+        // alternative, leaves most of the workgroup idle)
+        if (a.nvb < NT) {
             const int G = NT / a.nvb, v = tid & (a.nvb - 1), tg = tid / a.nvb;
             float xv[C], acc[BR];
             if (tg == 0) ldvec<TX, C>(x + brick_vox(a, k, v) * C, xv);  // in flight during the taps
@@ -358,8 +336,9 @@ __global__ __launch_bounds__(NT) void k_small_bwd(SArgs a, const TO *__restrict_
     SPROBE_DECL
     SPROBE(0)
     const Brick k = brick_of(a, blockIdx.x);
-    // phase 1's first UB positions (and, split taps, phase 2's voxel x) are loaded before the weight
-    // staging and its barrier as raw words: the load latencies overlap
+    // phase 1's first UB positions are loaded before the weight staging's LDS stores and barrier as
+    // raw words: the load latencies overlap (alternatives: the weights staged and synchronised
+    // first, or the split taps' voxel x loaded here too)
     int vis[UB];
     Raw<TO, C> gr_[UB];
     Raw<h16_t, BR> t3r[UB], t2r[UB];
@@ -374,15 +353,9 @@ __global__ __launch_bounds__(NT) void k_small_bwd(SArgs a, const TO *__restrict_
         }
     };
     const WStage<C, BR> ws(w1, w2, w3, tid);  // weights first: their LDS stores wait for them only
-    if (SMALL_BPRE == 0) {
-        ws.store(w2t, w1s, w3s, tid, true);
-        __syncthreads();
-    }
     load1(min(tid, a.hp - 1));
-    const bool split = SMALL_TSPLIT && a.nvb < NT;
-    Raw<TX, C> xr2;
-    if (split && SMALL_BPRE >= 2) xr2 = ldraw<TX, C>(x + brick_vox(a, k, tid & (a.nvb - 1)) * C);
-    if (SMALL_BPRE != 0) ws.store(w2t, w1s, w3s, tid, true);
+    const bool split = a.nvb < NT;
+    ws.store(w2t, w1s, w3s, tid, true);
     const Scal s = load_scal(p);
     float sp[kNScal];
 #pragma unroll
@@ -469,7 +442,7 @@ __global__ __launch_bounds__(NT) void k_small_bwd(SArgs a, const TO *__restrict_
             sp[7] += e;
             const float gv = gs[v * C + ci];
             gxv[ci] = gv + e;
-            const float u = belu(xv[ci] + s.b1a) + s.b1b;
+            const float u = elu_fast(xv[ci] + s.b1a) + s.b1b;
 #pragma unroll
             for (int o = 0; o < BR; ++o) {
                 acc1[ci][o] = fmaf(gv, t3v[o], acc1[ci][o]);
@@ -483,8 +456,7 @@ __global__ __launch_bounds__(NT) void k_small_bwd(SArgs a, const TO *__restrict_
     if (split) {  // the 27 taps over NT / nvb thread groups, as the forward's
         const int G = NT / a.nvb, v = tid & (a.nvb - 1), tg = tid / a.nvb;
         float xv[C], dt[BR];
-        if (SMALL_BPRE >= 2) unraw<TX, C>(xr2, xv);
-        else ldvec<TX, C>(x + brick_vox(a, k, v) * C, xv);  // every thread (exact wait counts)
+        ldvec<TX, C>(x + brick_vox(a, k, v) * C, xv);  // every thread (exact wait counts)
         taps(halo_pos(a, v), 27 * tg / G, 27 * (tg + 1) / G, dt);
         if (tg > 0) {
 #pragma unroll
@@ -736,12 +708,7 @@ bool plan(int batch, int C, int BR, int h, int w, int d, SArgs &a) {
     return true;
 }
 
-template <typename K>
-void allow_lds(K kern) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              int(160 * 1024 - 1024));
-    (void)hipGetLastError();
-}
+constexpr size_t kLdsOptIn = 160 * 1024 - 1024;  // dynamic LDS the brick kernels may ask for
 
 }  // namespace
 
@@ -805,11 +772,7 @@ int vq3d_preact_small_fwd_io(int32_t dtype, int32_t x_dtype, int32_t out_dtype, 
     const size_t lds = lds_fwd(a, branch) + size_t(NT) * branch * 4;  // + the tap-group partials
 #define F2(C_, B_, TX_, TO_)                                                                                   \
     {                                                                                                          \
-        static bool attr = false;                                                                              \
-        if (!attr) {                                                                                           \
-            allow_lds(k_small_fwd<C_, B_, TX_, TO_>);                                                          \
-            attr = true;                                                                                       \
-        }                                                                                                      \
+        opt_in_lds(k_small_fwd<C_, B_, TX_, TO_>, kLdsOptIn);                                                  \
         k_small_fwd<C_, B_, TX_, TO_><<<unsigned(a.nbricks), NT, lds, s>>>(a, (const TX_ *)x, w1, w2, w3, *p,  \
                                                                           (TO_ *)out, (h16_t *)t2, (h16_t *)t3); \
     }
@@ -891,11 +854,7 @@ int vq3d_preact_small_bwd_stages_io(int32_t stages, int32_t dtype, int32_t x_dty
     float *part = static_cast<float *>(workspace);
 #define B2(C_, B_, TX_, TO_)                                                                                   \
     {                                                                                                          \
-        static bool attr = false;                                                                              \
-        if (!attr) {                                                                                           \
-            allow_lds(k_small_bwd<C_, B_, TX_, TO_>);                                                          \
-            attr = true;                                                                                       \
-        }                                                                                                      \
+        opt_in_lds(k_small_bwd<C_, B_, TX_, TO_>, kLdsOptIn);                                                  \
         if (stages & 1)                                                                                        \
             k_small_bwd<C_, B_, TX_, TO_><<<unsigned(a.nbricks), NT, lds, s>>>(                                \
                 a, (const TO_ *)g, (const TX_ *)x, (const h16_t *)t2, (const h16_t *)t3, w1, w2, w3, *p, part,  \

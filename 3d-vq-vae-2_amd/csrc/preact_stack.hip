@@ -17,7 +17,9 @@
 // parameter gradient of every block.  One workgroup owns all of it, so each gradient entry has
 // exactly one adder and the scalar sums are fixed-order: deterministic.  Each block's weights
 // are staged into LDS while the previous block computes (register prefetch).
+#include "block_util.h"
 #include "engines.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -52,14 +54,7 @@ __device__ __forceinline__ int nbr(const SkArgs &a, int v, int tap, int sgn) {
     return ((b * a.H + h) * a.W + w) * a.D + d;
 }
 
-__device__ __forceinline__ float elu_d_act(float t, float b) {  // elu'(z) from t = elu(z) + b
-    const float z1 = t - b;
-    return z1 > 0.f ? 1.f : z1 + 1.f;
-}
-
-struct Scal {
-    float b1a, b1b, b2a, b2b, b3a, b3b, sc, b4;
-};
+// the block's scalars from its parameter table row (block_util.h's Scal)
 __device__ __forceinline__ Scal scal_of(const float *const *t) {
     return Scal{*t[3], *t[4], *t[5], *t[6], *t[7], *t[8], *t[9], *t[10]};
 }
@@ -417,20 +412,10 @@ __global__ __launch_bounds__(NT) void k_stack_bwd(SkArgs a, const T *__restrict_
 // transposed conv, gx and the three weight gradients with the voxels as the reduction axis).
 // Rounding points are the unfused bf16 path's (u1, t2, t3, gz3, gz1 rounded to bf16 as matrix
 // operands, fp32 accumulation); the residual stream and the gradient stream stay fp32.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int MC = 32, MB = 16;            // channels, branch
 constexpr int PF = 36, PU = 40, PT = 24;   // row pitches: fp32 streams, u1 (bf16), branch tensors (bf16)
 constexpr int MAXVM = 128;
 
-__device__ __forceinline__ f32x4 mfma(hx8 a, hx8 b, f32x4 c) {
-    return VQ3D_MFMA_16X16X32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ hx8 pack8(const float (&v)[8]) {
-    uint32_t w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = uint32_t(f2h(v[2 * j])) | (uint32_t(f2h(v[2 * j + 1])) << 16);
-    return __builtin_bit_cast(hx8, uint4{w[0], w[1], w[2], w[3]});
-}
 __device__ __forceinline__ hx8 rd8(const h16_t *p) { return __builtin_bit_cast(hx8, *reinterpret_cast<const uint4 *>(p)); }
 __device__ __forceinline__ hx8 zero8() { return __builtin_bit_cast(hx8, uint4{0u, 0u, 0u, 0u}); }
 // 8 bf16 at p[j * stride] (LDS)
@@ -946,7 +931,7 @@ __global__ __launch_bounds__(NT) void k_stackm_bwd(SkArgs a, const h16_t *__rest
 // the scale gradient (sum W3 . G3): waves 2, 3.  Each gradient entry has one adder.
 constexpr int PG = 40;  // row pitch of the bf16 g record copy
 #ifndef VQ3D_STACK_RCW
-#define VQ3D_STACK_RCW 4
+#define VQ3D_STACK_RCW 4  // the register chain's compute waves (timing experiments)
 #endif
 constexpr int RPART = VQ3D_STACK_RCW;  // k_stackr_bwd's scalar partials per block (one per compute wave)
 __global__ __launch_bounds__(NT) void k_stackm_wgrad(SkArgs a, const float *const *tab, float *const *gtab,
@@ -1064,9 +1049,6 @@ __global__ __launch_bounds__(NT) void k_stackm_wgrad(SkArgs a, const float *cons
 // forward / backward when the compute waves stored).  Compute waves without stores wait with
 // exact counts.  The ring is 3 deep (block b's slot is rewritten in block b + 3, after the store
 // waves' reads in block b + 1 and two barriers).  Rounding points are k_stackm_*'s.
-#ifndef VQ3D_STACK_RCW
-#define VQ3D_STACK_RCW 4
-#endif
 constexpr int RCW = VQ3D_STACK_RCW;      // compute waves; wave w owns column blocks w, w + RCW, ...
 constexpr int RSW = 4;                   // store waves
 constexpr int NH = MAXVM / 16 / RCW;     // column blocks per compute wave
@@ -1079,11 +1061,7 @@ static_assert(RIMG == FR_N, "the register chain's images fit the k_stackm image 
 constexpr int RPS = 8;                   // scalar partials per compute wave and block (k_stackm_bwd's ps order)
 constexpr int RRING = 3;
 constexpr int RPF = 3;                   // store waves' L2 prefetch distance (blocks)
-#if defined(VQ3D_STACK_EXP) && VQ3D_STACK_EXP == 2
-#define FR_REFILL(k0, k1)
-#else
 #define FR_REFILL(k0, k1) fr.load(img, nx, lane, k0, k1)
-#endif
 
 // phase clock probe (tools/probes/stack_probe.hip builds this file with VQ3D_STACK_PROBE): wave 0
 // stamps s_memtime at 5 points of every block into LDS and dumps them at the end
@@ -1200,13 +1178,7 @@ __device__ __forceinline__ f32x4 conv14(const RFrag &fr, const hx8 (&nb)[14]) {
 // exp through v_exp_f32 (2^x) directly: the chain is VALU-issue bound (one compute wave per SIMD,
 // 4 cycles per instruction), and expf's range reduction was ~11 instructions per call, a third of
 // the forward loop; the results are rounded to 16 bits (t2, t3) or feed fp32 gradients
-#ifndef VQ3D_STACK_FAST_EXP
-#define VQ3D_STACK_FAST_EXP 1
-#endif
-__device__ __forceinline__ float exp_f(float z) {
-    if constexpr (VQ3D_STACK_FAST_EXP) return __builtin_amdgcn_exp2f(z * 1.44269504088896341f);
-    else return expf(z);
-}
+__device__ __forceinline__ float exp_f(float z) { return __builtin_amdgcn_exp2f(z * 1.44269504088896341f); }
 __device__ __forceinline__ float elu_f(float z) { return z > 0.f ? z : exp_f(z) - 1.f; }
 // elu(z + a) + b with the bias folds precomputed per block (EluB): one compare, one add, one fma,
 // the exp and one add per element instead of two adds, a multiply, the exp, an add and the compare
@@ -1214,13 +1186,10 @@ struct EluB {
     float na, ab, al, bm;  // -a, a + b, a log2(e), b - 1
     __device__ __forceinline__ EluB(float a, float b) : na(-a), ab(a + b), al(a * 1.44269504088896341f), bm(b - 1.f) {}
     __device__ __forceinline__ float operator()(float z) const {
-        float e;
-        if constexpr (VQ3D_STACK_FAST_EXP) e = __builtin_amdgcn_exp2f(fmaf(z, 1.44269504088896341f, al)) + bm;
-        else e = expf(z - na) + bm;
+        const float e = __builtin_amdgcn_exp2f(fmaf(z, 1.44269504088896341f, al)) + bm;
         return z > na ? z + ab : e;
     }
 };
-__device__ __forceinline__ uint32_t pk2h(float a, float b) { return uint32_t(f2h(a)) | (uint32_t(f2h(b)) << 16); }
 __device__ __forceinline__ float lo_h(uint32_t u) { return h2f_lo(u & 0xffffu); }
 __device__ __forceinline__ float hi_h(uint32_t u) { return h2f_lo(u >> 16); }
 
@@ -1310,11 +1279,7 @@ __global__ __launch_bounds__(RNT) void k_stackr_fwd(SkArgs a, const h16_t *__res
         RPROBE(blk, 0)
         // the next block (the last block reloads itself: every load unconditional, so the
         // compiler's waits count exactly), its scalars a block ahead
-#if defined(VQ3D_STACK_EXP) && VQ3D_STACK_EXP == 1
-        const int nx = 0;
-#else
         const int nx = min(blk + 1, a.nblk - 1);
-#endif
         vc = ldg(pn);
         pn = row_ptr(tab, min(blk + 2, a.nblk - 1), lane);
         const RfLds l = rf_slot(smem, nv, blk % RRING);
@@ -1338,7 +1303,7 @@ __global__ __launch_bounds__(RNT) void k_stackr_fwd(SkArgs a, const h16_t *__res
             if (!act[h]) continue;
             const f32x4 c = a2[h];
             *reinterpret_cast<u32x2 *>(l.t2s + pl_off(vv[h], 4 * kb)) =
-                u32x2{pk2h(e2(c[0]), e2(c[1])), pk2h(e2(c[2]), e2(c[3]))};
+                u32x2{pk2(e2(c[0]), e2(c[1])), pk2(e2(c[2]), e2(c[3]))};
         }
         RPROBE(blk, 1)
         __syncthreads();
@@ -1360,7 +1325,7 @@ __global__ __launch_bounds__(RNT) void k_stackr_fwd(SkArgs a, const h16_t *__res
         for (int h = 0; h < NH; ++h) {
             if (!act[h]) continue;
             const f32x4 c = cc[h];
-            t3p[h] = u32x2{pk2h(e3(c[0]), e3(c[1])), pk2h(e3(c[2]), e3(c[3]))};
+            t3p[h] = u32x2{pk2(e3(c[0]), e3(c[1])), pk2(e3(c[2]), e3(c[3]))};
             *reinterpret_cast<u32x2 *>(l.t3s + pl_off(vv[h], 4 * kb)) = t3p[h];
         }
         RPROBE(blk, 3)
@@ -1520,8 +1485,8 @@ __global__ __launch_bounds__(RNT) void k_stackr_bwd(SkArgs a, const h16_t *__res
             const float *q = gv[h];
 #pragma unroll
             for (int j = 0; j < 8; ++j) ps[0] += q[j];
-            *reinterpret_cast<u32x2 *>(l.gs + v * PG + 4 * kb) = u32x2{pk2h(q[0], q[1]), pk2h(q[2], q[3])};
-            *reinterpret_cast<u32x2 *>(l.gs + v * PG + 16 + 4 * kb) = u32x2{pk2h(q[4], q[5]), pk2h(q[6], q[7])};
+            *reinterpret_cast<u32x2 *>(l.gs + v * PG + 4 * kb) = u32x2{pk2(q[0], q[1]), pk2(q[2], q[3])};
+            *reinterpret_cast<u32x2 *>(l.gs + v * PG + 16 + 4 * kb) = u32x2{pk2(q[4], q[5]), pk2(q[6], q[7])};
             const f32x4 a3 = mfma(fr[0], pack8(gv[h]), f32x4{0.f, 0.f, 0.f, 0.f});
             const float t3v[4] = {s3[h].x, s3[h].y, s3[h].z, s3[h].w};
             float zq[4];
@@ -1532,7 +1497,7 @@ __global__ __launch_bounds__(RNT) void k_stackr_bwd(SkArgs a, const h16_t *__res
                 ps[2] += g3;
                 ps[3] += zq[i];
             }
-            *reinterpret_cast<u32x2 *>(l.z3s + pl_off(v, 4 * kb)) = u32x2{pk2h(zq[0], zq[1]), pk2h(zq[2], zq[3])};
+            *reinterpret_cast<u32x2 *>(l.z3s + pl_off(v, 4 * kb)) = u32x2{pk2(zq[0], zq[1]), pk2(zq[2], zq[3])};
         }
         fr.load(img, nx, lane, 0, 1);
 #pragma unroll
@@ -1562,7 +1527,7 @@ __global__ __launch_bounds__(RNT) void k_stackr_bwd(SkArgs a, const h16_t *__res
                 ps[4] += c[i];
                 ps[5] += z[i];
             }
-            z1p[h] = u32x2{pk2h(z[0], z[1]), pk2h(z[2], z[3])};
+            z1p[h] = u32x2{pk2(z[0], z[1]), pk2(z[2], z[3])};
             *reinterpret_cast<u32x2 *>(l.z1s + pl_off(vv[h], 4 * kb)) = z1p[h];
         }
         RPROBE(blk, 3)
@@ -1580,9 +1545,7 @@ __global__ __launch_bounds__(RNT) void k_stackr_bwd(SkArgs a, const h16_t *__res
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float gt1 = j < 4 ? o0[j] : o1[j - 4];
-                const float e = xs[j] > nb1a ? 1.f
-                                : (VQ3D_STACK_FAST_EXP ? __builtin_amdgcn_exp2f(fmaf(xs[j], 1.44269504088896341f, b1al))
-                                                       : expf(xs[j] - nb1a));
+                const float e = xs[j] > nb1a ? 1.f : __builtin_amdgcn_exp2f(fmaf(xs[j], 1.44269504088896341f, b1al));
                 ps[6] += gt1;
                 ps[7] += gt1 * e;
                 gv[h][j] += gt1 * e;
@@ -1613,11 +1576,7 @@ size_t lds_wgrad(int nv) { return size_t(nv) * (4 * PT + PU + PG) * 2 + size_t((
 
 bool mfma_ok(const SkArgs &a) { return a.C == MC && a.B == MB && a.nv % 32 == 0 && a.nv <= MAXVM; }
 
-bool lds_opt_in(const void *k) {
-    (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(160 * 1024));
-    (void)hipGetLastError();
-    return true;
-}
+constexpr size_t kLdsAll = 160 * 1024;  // the chain kernels may take the whole LDS
 
 // which matrix-core chain runs: 'r' the register chain (default), 'm' the LDS-phase k_stackm_*
 // (VQ3D_STACK_CHAIN=m, kept for A/B measurements)
@@ -1674,29 +1633,25 @@ int vq3d_preact_stack_fwd(int32_t dtype, int32_t nblocks, int32_t batch, int32_t
     hipStream_t s = as_stream(stream);
     const size_t lds = lds_bytes(a, false);
     if (dtype == VQ3D_HALF && mfma_ok(a)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stackm_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  int(160 * 1024));
         h16_t *img = reinterpret_cast<h16_t *>(saved + size_t(nblocks) * a.nv * (a.C + 2 * a.B));
         if (stack_chain() == 'r') {
             k_stackr_pack<false><<<nblocks, 256, 0, s>>>(params, img);
-            static const bool opt = lds_opt_in(reinterpret_cast<const void *>(k_stackr_fwd<true>)) &&
-                                    lds_opt_in(reinterpret_cast<const void *>(k_stackr_fwd<false>));
-            (void)opt;
+            opt_in_lds(k_stackr_fwd<true>, kLdsAll);
+            opt_in_lds(k_stackr_fwd<false>, kLdsAll);
             if (a.nv == MAXVM)
                 k_stackr_fwd<true><<<1, RNT, lds_rf(a.nv), s>>>(a, (const h16_t *)x, params, (h16_t *)out, saved, img);
             else
                 k_stackr_fwd<false><<<1, RNT, lds_rf(a.nv), s>>>(a, (const h16_t *)x, params, (h16_t *)out, saved, img);
         } else {
+            opt_in_lds(k_stackm_fwd, kLdsAll);
             k_stackm_pack<false><<<nblocks, NT, 0, s>>>(params, img);
             k_stackm_fwd<<<1, NT, lds_m(a.nv), s>>>(a, (const h16_t *)x, params, (h16_t *)out, saved, img);
         }
     } else if (dtype == VQ3D_HALF) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stack_fwd<h16_t>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(160 * 1024));
+        opt_in_lds(k_stack_fwd<h16_t>, kLdsAll);
         k_stack_fwd<h16_t><<<1, NT, lds, s>>>(a, (const h16_t *)x, params, (h16_t *)out, saved);
     } else if (dtype == VQ3D_F32) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stack_fwd<float>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(160 * 1024));
+        opt_in_lds(k_stack_fwd<float>, kLdsAll);
         k_stack_fwd<float><<<1, NT, lds, s>>>(a, (const float *)x, params, (float *)out, saved);
     } else {
         return fail("preact_stack_fwd: dtype");
@@ -1713,17 +1668,14 @@ int vq3d_preact_stack_bwd(int32_t dtype, int32_t nblocks, int32_t batch, int32_t
     hipStream_t s = as_stream(stream);
     const size_t lds = lds_bytes(a, true);
     if (dtype == VQ3D_HALF && mfma_ok(a)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stackm_bwd<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(160 * 1024));
+        opt_in_lds(k_stackm_bwd<false>, kLdsAll);
         k_stackm_bwd<false><<<1, NT, lds_m(a.nv), s>>>(a, (const h16_t *)g, params, grads, saved, (h16_t *)gx, nullptr,
                                                        nullptr);
     } else if (dtype == VQ3D_HALF) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stack_bwd<h16_t>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(160 * 1024));
+        opt_in_lds(k_stack_bwd<h16_t>, kLdsAll);
         k_stack_bwd<h16_t><<<1, NT, lds, s>>>(a, (const h16_t *)g, params, grads, saved, (h16_t *)gx);
     } else if (dtype == VQ3D_F32) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stack_bwd<float>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(160 * 1024));
+        opt_in_lds(k_stack_bwd<float>, kLdsAll);
         k_stack_bwd<float><<<1, NT, lds, s>>>(a, (const float *)g, params, grads, saved, (float *)gx);
     } else {
         return fail("preact_stack_bwd: dtype");
@@ -1756,9 +1708,8 @@ int vq3d_preact_stack_bwd_ws(int32_t dtype, int32_t nblocks, int32_t batch, int3
     float *part = reinterpret_cast<float *>(img + size_t(nblocks) * FR_N);
     if (stack_chain() == 'r') {
         k_stackr_pack<true><<<nblocks, 256, 0, s>>>(params, img);
-        static const bool opt = lds_opt_in(reinterpret_cast<const void *>(k_stackr_bwd<true>)) &&
-                                lds_opt_in(reinterpret_cast<const void *>(k_stackr_bwd<false>));
-        (void)opt;
+        opt_in_lds(k_stackr_bwd<true>, kLdsAll);
+        opt_in_lds(k_stackr_bwd<false>, kLdsAll);
         if (a.nv == MAXVM)
             k_stackr_bwd<true><<<1, RNT, lds_rb(a.nv), s>>>(a, (const h16_t *)g, params, saved, (h16_t *)gx,
                                                             (h16_t *)workspace, part, img);
@@ -1767,8 +1718,7 @@ int vq3d_preact_stack_bwd_ws(int32_t dtype, int32_t nblocks, int32_t batch, int3
                                                              (h16_t *)workspace, part, img);
         k_stackm_wgrad<<<nblocks, NT, lds_wgrad(a.nv), s>>>(a, params, grads, saved, (const h16_t *)workspace, part);
     } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stackm_bwd<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(160 * 1024));
+        opt_in_lds(k_stackm_bwd<true>, kLdsAll);
         k_stackm_pack<true><<<nblocks, NT, 0, s>>>(params, img);
         k_stackm_bwd<true><<<1, NT, lds_m(a.nv), s>>>(a, (const h16_t *)g, params, grads, saved, (h16_t *)gx,
                                                       (h16_t *)workspace, img);

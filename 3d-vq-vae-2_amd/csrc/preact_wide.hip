@@ -29,7 +29,8 @@
 //   A: A[row][8 kb + j]   B: B[8 kb + j][row]   D: D[4 kb + j][row]   (j = 0..7 / 0..3)
 // A wave owns one 16-column n-tile of the 36 branch channels and half of the m-tiles (6 waves),
 // so no cross-wave sums.
-#include "common.h"
+#include "block_util.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -37,8 +38,6 @@
 namespace vq3d {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C = 72, BR = 36;                         // block / branch channels
 #ifndef WIDE_TW
@@ -75,18 +74,6 @@ struct WArgs {
     int nth, ntw, ntd, ntiles;
 };
 
-__device__ __forceinline__ int wrapm(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
-__device__ __forceinline__ float bf(uint32_t u16) { return h2f_lo(u16); }
-__device__ __forceinline__ float elu_d_act(float t, float b) {  // elu'(z) from t = elu(z) + b
-    const float z1 = t - b;
-    return z1 > 0.f ? 1.f : z1 + 1.f;
-}
-// elu with the hardware exp (v_exp_f32): every result is rounded to bf16 or feeds a bf16 operand
-__device__ __forceinline__ float elu_f(float z) { return z > 0.f ? z : __expf(z) - 1.f; }
-__device__ __forceinline__ f32x4 mfma(hx8 a, hx8 b, f32x4 c) {
-    return VQ3D_MFMA_16X16X32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ uint32_t pk(float a, float b) { return uint32_t(f2h(a)) | (uint32_t(f2h(b)) << 16); }
 // 8 bf16 from LDS, 8-byte aligned
 __device__ __forceinline__ hx8 ld8(const h16_t *p) {
     const uint2 *q = reinterpret_cast<const uint2 *>(p);
@@ -95,15 +82,6 @@ __device__ __forceinline__ hx8 ld8(const h16_t *p) {
 }
 // 8 bf16 from LDS, 16-byte aligned
 __device__ __forceinline__ hx8 ld16(const h16_t *p) { return *reinterpret_cast<const hx8 *>(p); }
-// 8 consecutive bf16 at any element offset (4-byte aligned base): five dwords + v_alignbyte
-__device__ __forceinline__ hx8 read8(const h16_t *base, int off) {
-    const uint32_t *q = reinterpret_cast<const uint32_t *>(base + (off & ~1));
-    const uint32_t sh = uint32_t(off & 1) * 2u;
-    const uint32_t u0 = q[0], u1 = q[1], u2 = q[2], u3 = q[3], u4 = q[4];
-    const uint4 r = {__builtin_amdgcn_alignbyte(u1, u0, sh), __builtin_amdgcn_alignbyte(u2, u1, sh),
-                     __builtin_amdgcn_alignbyte(u3, u2, sh), __builtin_amdgcn_alignbyte(u4, u3, sh)};
-    return __builtin_bit_cast(hx8, r);
-}
 // fragment f of a block image for this lane
 __device__ __forceinline__ hx8 frag(const uint4 *__restrict__ img, int f, int lane) {
     return __builtin_bit_cast(hx8, img[f * 64 + lane]);
@@ -112,13 +90,6 @@ __device__ __forceinline__ hx8 frag(const uint4 *__restrict__ img, int f, int la
 // 2k (lo) and 2k + 1 (hi)
 __device__ __forceinline__ uint32_t tlo(uint32_t a, uint32_t b) { return (a & 0xffffu) | (b << 16); }
 __device__ __forceinline__ uint32_t thi(uint32_t a, uint32_t b) { return (a >> 16) | (b & 0xffff0000u); }
-
-struct Scal {
-    float b1a, b1b, b2a, b2b, b3a, b3b, sc, b4;
-};
-__device__ __forceinline__ Scal load_scal(const vq3d_preact_params &p) {
-    return Scal{*p.bias1a, *p.bias1b, *p.bias2a, *p.bias2b, *p.bias3a, *p.bias3b, *p.scale, *p.bias4};
-}
 
 struct Org {
     int b, h0, w0, d0;
@@ -190,10 +161,10 @@ __device__ __forceinline__ float stage_halo_f32(const int *segv, const float *__
             const int seg = i / Q, c4 = i - seg * Q;
             float4 t = v[u];
             if (ELU) {
-                t.x = elu_f(t.x + b1a) + b1b;
-                t.y = elu_f(t.y + b1a) + b1b;
-                t.z = elu_f(t.z + b1a) + b1b;
-                t.w = elu_f(t.w + b1a) + b1b;
+                t.x = elu_fast(t.x + b1a) + b1b;
+                t.y = elu_fast(t.y + b1a) + b1b;
+                t.z = elu_fast(t.z + b1a) + b1b;
+                t.w = elu_fast(t.w + b1a) + b1b;
             } else {
                 const int line = seg / NP, pos = seg - line * NP, lh = line / LW, lw = line - lh * LW;
                 if (pos >= 1 && pos <= TD && lh >= 1 && lh <= TH && lw >= 1 && lw <= TW) {
@@ -201,7 +172,7 @@ __device__ __forceinline__ float stage_halo_f32(const int *segv, const float *__
                     reinterpret_cast<float4 *>(interior + (((lh - 1) * TW + lw - 1) * TD + pos - 1) * C)[c4] = t;
                 }
             }
-            *reinterpret_cast<uint2 *>(dst + seg * C + 4 * c4) = uint2{pk(t.x, t.y), pk(t.z, t.w)};
+            *reinterpret_cast<uint2 *>(dst + seg * C + 4 * c4) = uint2{pk2(t.x, t.y), pk2(t.z, t.w)};
         }
     }
     return isum;
@@ -282,7 +253,8 @@ __global__ __launch_bounds__(64) void k_wide_pack(const float *const *__restrict
         }
         v[j] = x;
     }
-    img[(int64_t(blk) * NFRAG + f) * 64 + l] = uint4{pk(v[0], v[1]), pk(v[2], v[3]), pk(v[4], v[5]), pk(v[6], v[7])};
+    img[(int64_t(blk) * NFRAG + f) * 64 + l] =
+        uint4{pk2(v[0], v[1]), pk2(v[2], v[3]), pk2(v[4], v[5]), pk2(v[6], v[7])};
 }
 
 // ============================================================================================ forward
@@ -322,7 +294,7 @@ __global__ __launch_bounds__(NT) void k_wide_fwd(WArgs a, const float *__restric
         for (int k = 0; k < KS1; ++k) acc = mfma(ld16(u1h + (16 * m + row) * C + 32 * k + 8 * kb), f1[k], acc);
         if (ob < BR) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) t2h[(16 * m + 4 * kb + j) * BR + ob] = f2h(elu_f(acc[j] + s.b2a) + s.b2b);
+            for (int j = 0; j < 4; ++j) t2h[(16 * m + 4 * kb + j) * BR + ob] = f2h(elu_fast(acc[j] + s.b2a) + s.b2b);
         }
     }
     __syncthreads();
@@ -360,7 +332,7 @@ __global__ __launch_bounds__(NT) void k_wide_fwd(WArgs a, const float *__restric
         for (int mm = 0; mm < MPW; ++mm)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                t3s[(16 * (MPW * hf + mm) + 4 * kb + j) * BR + ob] = f2h(elu_f(acc3[mm][j] + s.b3a) + s.b3b);
+                t3s[(16 * (MPW * hf + mm) + 4 * kb + j) * BR + ob] = f2h(elu_fast(acc3[mm][j] + s.b3a) + s.b3b);
     }
     __syncthreads();
     if (t3o) tile_to_global<false>(runv, t3s, t3o);
@@ -469,7 +441,7 @@ __global__ __launch_bounds__(NT) void k_wide_bwd_data(WArgs a, const float *__re
                 s4 += (t.x + t.y) + (t.z + t.w);  // the fp32 value is kept for the gx epilogue
                 reinterpret_cast<float4 *>(gI + (((lh - 1) * TW + lw - 1) * TD + pos - 1) * C)[c4] = t;
             }
-            *reinterpret_cast<uint2 *>(gh + seg * C + 4 * c4) = uint2{pk(t.x, t.y), pk(t.z, t.w)};
+            *reinterpret_cast<uint2 *>(gh + seg * C + 4 * c4) = uint2{pk2(t.x, t.y), pk2(t.z, t.w)};
         }
     }
     __syncthreads();
@@ -490,7 +462,7 @@ __global__ __launch_bounds__(NT) void k_wide_bwd_data(WArgs a, const float *__re
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int hv = 16 * m + 4 * kb + j;
-                const float t3v = bf(t3h[hv * BR + ob]), gt3 = s.sc * acc[j];
+                const float t3v = h2f_lo(t3h[hv * BR + ob]), gt3 = s.sc * acc[j];
                 const float z = gt3 * elu_d_act(t3v, s.b3b);
                 z3h[hv * BR + ob] = f2h(z);
                 if (mj & (1u << j)) {
@@ -523,7 +495,7 @@ __global__ __launch_bounds__(NT) void k_wide_bwd_data(WArgs a, const float *__re
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int vv = 16 * m + 4 * kb + j;
-                const float z1 = acc[j] * elu_d_act(bf(t2s[vv * BR + ob]), s.b2b);
+                const float z1 = acc[j] * elu_d_act(h2f_lo(t2s[vv * BR + ob]), s.b2b);
                 s2b += acc[j];
                 s2a += z1;
                 z1s[vv * BR + ob] = f2h(z1);
@@ -732,10 +704,10 @@ __device__ __forceinline__ void wide_wgrad(const WArgs &a, int nch, const float 
                 for (int k = 0; k < 4; ++k) {
                     float lv = l4[k], hv = h4[k];
                     if (!which) {
-                        lv = elu_f(lv + s.b1a) + s.b1b;
-                        hv = elu_f(hv + s.b1a) + s.b1b;
+                        lv = elu_fast(lv + s.b1a) + s.b1b;
+                        hv = elu_fast(hv + s.b1a) + s.b1b;
                     }
-                    reinterpret_cast<uint32_t *>(dT + (4 * q + k) * SP + 2 * pr)[0] = pk(lv, hv);
+                    reinterpret_cast<uint32_t *>(dT + (4 * q + k) * SP + 2 * pr)[0] = pk2(lv, hv);
                 }
             }
         }
@@ -882,18 +854,6 @@ constexpr size_t kWgLdsB = size_t((48 + 48 + 80 + 80) * SP) * 2;
 constexpr size_t kWgLds = kWgLdsA > kWgLdsB ? kWgLdsA : kWgLdsB;
 static_assert(kFwdLds <= 160 * 1024 && kBwdLds <= 160 * 1024 && kWgLds <= 160 * 1024, "LDS");
 
-void set_lds_limits() {
-    static bool done = false;
-    if (done) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_wide_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              int(kFwdLds));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_wide_bwd_data),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, int(kBwdLds));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_wide_wgrad), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              int(kWgLds));
-    done = true;
-}
-
 struct WsLayout {
     size_t gz3, gz1, p1, p2a, p2b, total;
 };
@@ -945,7 +905,7 @@ int vq3d_preact_wide_fwd(int32_t dtype, int32_t batch, int32_t channels, int32_t
         return fail("preact_wide_fwd: shape outside the fused wide-block kernels");
     if (!x || !image || !p || !out) return fail("preact_wide_fwd: null pointer");
     if (static_cast<const void *>(x) == static_cast<const void *>(out)) return fail("preact_wide_fwd: out aliases x");
-    set_lds_limits();
+    opt_in_lds(k_wide_fwd, kFwdLds);
     const WArgs a = make_args(batch, h, w, dd);
     k_wide_fwd<<<a.ntiles, NT, kFwdLds, as_stream(stream)>>>(a, x, static_cast<const uint4 *>(image), *p, out,
                                                              static_cast<h16_t *>(t2), static_cast<h16_t *>(t3));
@@ -967,7 +927,7 @@ int vq3d_preact_wide_bwd_data(int32_t dtype, int32_t batch, int32_t channels, in
     const WsLayout l = ws_layout(batch, h, w, dd);
     if (workspace_bytes < l.total) return fail("preact_wide_bwd_data: workspace too small");
     if (static_cast<const void *>(gx) == static_cast<const void *>(g)) return fail("preact_wide_bwd_data: gx aliases g");
-    set_lds_limits();
+    opt_in_lds(k_wide_bwd_data, kBwdLds);
     char *ws = static_cast<char *>(workspace);
     const WArgs a = make_args(batch, h, w, dd);
     k_wide_bwd_data<<<a.ntiles, NT, kBwdLds, as_stream(stream)>>>(
@@ -1018,13 +978,7 @@ int vq3d_preact_wide_wgrad_run(int32_t dtype, int32_t nblocks, int32_t batch, in
         return fail("preact_wide_wgrad_run: stride below the workspace size or unaligned");
     for (int i = 0; i < nblocks; ++i)
         if (!g[i] || !x[i] || !t2[i] || !t3[i]) return fail("preact_wide_wgrad_run: null tensor pointer");
-    set_lds_limits();
-    static bool init = false;
-    if (!init) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_wide_wgrad_run),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(kWgLds));
-        init = true;
-    }
+    opt_in_lds(k_wide_wgrad_run, kWgLds);
     const WArgs a = make_args(batch, h, w, dd);
     const int nch = int(int64_t(batch) * h * w * dd / CHV), nchb = int(int64_t(batch) * h * w * dd / SUBV);
     const char *b0 = static_cast<const char *>(workspaces);
@@ -1059,7 +1013,7 @@ int vq3d_preact_wide_bwd_weight_stages(int32_t stages, int32_t dtype, int32_t ba
         return fail("preact_wide_bwd_weight: every gradient buffer is required");
     const WsLayout l = ws_layout(batch, h, w, dd);
     if (workspace_bytes < l.total) return fail("preact_wide_bwd_weight: workspace too small");
-    set_lds_limits();
+    opt_in_lds(k_wide_wgrad, kWgLds);
     const char *ws = static_cast<const char *>(workspace);
     const WArgs a = make_args(batch, h, w, dd);
     const int nch = int(int64_t(batch) * h * w * dd / CHV), nchb = int(int64_t(batch) * h * w * dd / SUBV);

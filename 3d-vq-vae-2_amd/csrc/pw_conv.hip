@@ -14,6 +14,7 @@
 // writes its output row back to the LDS out slab.
 #include "conv_epi.h"
 #include "engines.h"
+#include "launch.h"
 
 #include <type_traits>
 
@@ -644,7 +645,6 @@ static int launch_pw_sg(const vq3d_conv_desc *d, bool dgrad, const void *in, con
 // W[k][n]) lives in LDS as packed B fragments.  Operands are bf16, as the reference's autocast
 // 1x1 convs run in fp16 (the VALU kernels above keep the weights fp32).
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // 4 consecutive bf16 (8-byte aligned when `vec`) <-> fp32; `cnt` of them valid
 __device__ __forceinline__ void ld4(const h16_t *p, bool vec, int cnt, float (&o)[4]) {
@@ -987,15 +987,7 @@ int launch_pw1(const vq3d_conv_desc *d, bool dgrad, const void *in, const void *
 #define L(C)                                                                                                    \
     case C: {                                                                                                   \
         auto kern = dgrad ? k_pw2<T, C, true> : k_pw2<T, C, false>;                                             \
-        static bool attr = false;                                                                               \
-        if (!attr) {                                                                                            \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_pw2<T, C, true>),                        \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);                  \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_pw2<T, C, false>),                       \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);                  \
-            (void)hipGetLastError();                                                                            \
-            attr = true;                                                                                        \
-        }                                                                                                       \
+        opt_in_lds(kern, 150 * 1024);                                                                           \
         kern<<<nbx, SEG, lds, s>>>(a, (const T *)in, (const T *)in2, w, fe, be, gscale, (T *)out, (T *)out2,    \
                                    dpre, dpost, part, tk);                                                      \
     } break;

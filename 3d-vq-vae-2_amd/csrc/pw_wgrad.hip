@@ -359,7 +359,6 @@ __global__ __launch_bounds__(256) void k_pw_wgrad_reduce(const float *__restrict
 // VC voxels is contiguous); both operands come through the transposing ds_read_b64_tr_b16.  Waves
 // split the co tiles (nwm of them) and the chunk's K-steps (4 / nwm); per-workgroup partials are
 // combined over the K-split waves in a fixed order and written like k_pw_wgrad's.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
@@ -455,7 +454,7 @@ __global__ __launch_bounds__(256) void k_pw_wgrad_mma(WmArgs a, const h16_t *__r
                 for (int j = 0; j < 4; ++j) {
                     const float lo = pro.apply(h2f_lo(w[j]));
                     const float hi = pro.apply(h2f_hi(w[j]));
-                    w[j] = uint32_t(f2h(lo)) | (uint32_t(f2h(hi)) << 16);
+                    w[j] = pk2(lo, hi);
                 }
             if (C % 8 == 0) {  // the unit is 8 channels of one voxel
                 const int v = e / C, c = e - v * C;

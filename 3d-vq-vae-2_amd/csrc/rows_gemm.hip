@@ -15,12 +15,11 @@
 // holds 4 consecutive output channels of one voxel: 8-byte vector stores, bias added in fp32.
 // Workgroup: 4 waves x 16 voxels x 64 outputs; grid: voxel tiles x 64-output tiles.
 #include "engines.h"
+#include "launch.h"
 
 namespace vq3d {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RG_M = 64;   // voxels per workgroup (4 waves x 16)
 constexpr int RG_N = 64;   // outputs per workgroup (4 MFMA tiles)
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(256) void k_rows_gemm(RgArgs a, const h16_t *__rest
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = acc[t][j] + (bias ? bias[n + j] : 0.f);
             *reinterpret_cast<u32x2 *>(y + v * a.ldy + n) =
-                u32x2{uint32_t(f2h(o[0])) | (uint32_t(f2h(o[1])) << 16), uint32_t(f2h(o[2])) | (uint32_t(f2h(o[3])) << 16)};
+                u32x2{pk2(o[0], o[1]), pk2(o[2], o[3])};
         }
     }
 }
@@ -138,15 +137,8 @@ int launch_rows_gemm(int64_t nrows, int k, int n, const void *x, int64_t ldx, co
     const size_t lds = size_t(RG_N) * a.pitch * sizeof(h16_t);
     const dim3 grid{unsigned((nrows + RG_M - 1) / RG_M), unsigned((n + RG_N - 1) / RG_N), 1u};
     // above 64 KB of dynamic LDS (k > 472) the kernel must opt in (gfx950: 160 KB per workgroup)
-    static const bool opt_in = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rows_gemm<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(RG_N * (RG_KMAX + 8) * 2));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rows_gemm<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(RG_N * (RG_KMAX + 8) * 2));
-        (void)hipGetLastError();
-        return true;
-    }();
-    (void)opt_in;
+    constexpr size_t kLdsOptIn = size_t(RG_N) * (RG_KMAX + 8) * 2;
+    opt_in_lds(trans_w ? k_rows_gemm<true> : k_rows_gemm<false>, kLdsOptIn);
     if (trans_w)
         k_rows_gemm<true><<<grid, 256, lds, s>>>(a, (const h16_t *)x, (const h16_t *)w, bias, (h16_t *)y);
     else

@@ -17,7 +17,9 @@
 //           activation scalar gradients.
 // Scalar gradients are fixed-order block sums; weight gradients are added (+=) to the fp32
 // gradient buffers, each entry by exactly one thread.
+#include "block_util.h"
 #include "engines.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -47,11 +49,6 @@ __device__ __forceinline__ int nbr(const TArgs &a, int v, int tap, int sgn) {
     w = w < 0 ? w + a.W : (w >= a.W ? w - a.W : w);
     d = d < 0 ? d + a.D : (d >= a.D ? d - a.D : d);
     return ((b * a.H + h) * a.W + w) * a.D + d;
-}
-
-__device__ __forceinline__ float elu_d_act(float t, float b) {  // elu'(z) from t = elu(z) + b
-    const float z1 = t - b;
-    return z1 > 0.f ? 1.f : z1 + 1.f;
 }
 
 // put(i, src[i]) for the n elements of a 16-byte aligned array: 16-byte loads, four of them in
@@ -87,23 +84,6 @@ __device__ __forceinline__ void load_act(const T *__restrict__ src, float *dst, 
 
 __device__ __forceinline__ void load_f(const float *__restrict__ src, float *dst, int n) {
     stage(src, n, [&](int i, float v) { dst[i] = v; });
-}
-
-struct Scal {
-    float b1a, b1b, b2a, b2b, b3a, b3b, scale, b4;
-};
-
-__device__ __forceinline__ Scal load_scal(const vq3d_preact_params &p) {
-    Scal s;
-    s.b1a = *p.bias1a;
-    s.b1b = *p.bias1b;
-    s.b2a = *p.bias2a;
-    s.b2b = *p.bias2b;
-    s.b3a = *p.bias3a;
-    s.b3b = *p.bias3b;
-    s.scale = *p.scale;
-    s.b4 = *p.bias4;
-    return s;
 }
 
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -214,7 +194,7 @@ __global__ __launch_bounds__(NTF) void k_tiny_fwd(TArgs a, const T *__restrict__
         for (int c = 0; c < a.B; ++c) fma4(acc, tr[c], ld4(w3t + c * a.C + o0));
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            st(out + v * a.C + o0 + j, acc[j] * sc.scale + sc.b4 + xs[v * a.C + o0 + j]);
+            st(out + v * a.C + o0 + j, acc[j] * sc.sc + sc.b4 + xs[v * a.C + o0 + j]);
     }
 }
 
@@ -262,7 +242,7 @@ __global__ __launch_bounds__(NTA) void k_tiny_bwd_a(TArgs a, const T *__restrict
         for (int co = 0; co < a.C; co += 4) dot4x4(acc, ld4(gs + v * a.C + co), w3t + c0 * a.C + co, a.C);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float h3 = acc[j] * sc.scale;
+            const float h3 = acc[j] * sc.sc;
             const float z = h3 * elu_d_act(t3[v * a.B + c0 + j], sc.b3b);
             p_b3b += h3;
             p_b3a += z;
@@ -299,7 +279,7 @@ __global__ __launch_bounds__(NTA) void k_tiny_bwd_a(TArgs a, const T *__restrict
         const int co = e / a.B, c = e - co * a.B;
         float sum = 0.f;
         for (int v = 0; v < a.nv; ++v) sum = fmaf(gs[v * a.C + co], t3[v * a.B + c], sum);
-        if (gr.dw3) atomicAdd(gr.dw3 + e, sum * sc.scale);
+        if (gr.dw3) atomicAdd(gr.dw3 + e, sum * sc.sc);
         p_sc = fmaf(w3t[c * a.C + co], sum, p_sc);
     }
     for (int e = tid; e < a.nv * a.C; e += NTA) p_b4 += gs[e];
@@ -400,13 +380,6 @@ int check(int batch, int C, int B, int H, int W, int D, TArgs &a) {
     return 0;
 }
 
-template <typename K>
-void allow_lds(K kern) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              int(kLdsMax));
-    (void)hipGetLastError();
-}
-
 }  // namespace
 
 }  // namespace vq3d
@@ -435,12 +408,8 @@ int vq3d_preact_tiny_fwd(int32_t dtype, int32_t batch, int32_t channels, int32_t
     if (int r = check(batch, channels, branch, h, w, dd, a)) return r;
     if (!x || !w1 || !w2 || !w3 || !p || !out || !saved) return fail("preact_tiny_fwd: null pointer");
     hipStream_t s = as_stream(stream);
-    static bool attr = false;
-    if (!attr) {
-        allow_lds(k_tiny_fwd<h16_t>);
-        allow_lds(k_tiny_fwd<float>);
-        attr = true;
-    }
+    opt_in_lds(k_tiny_fwd<h16_t>, kLdsMax);
+    opt_in_lds(k_tiny_fwd<float>, kLdsMax);
     const unsigned nwg = unsigned((a.nv + VPW - 1) / VPW);
     if (dtype == VQ3D_HALF)
         k_tiny_fwd<h16_t><<<nwg, NTF, lds_fwd(a), s>>>(a, (const h16_t *)x, w1, w2, w3, *p, (h16_t *)out, saved);
@@ -458,14 +427,10 @@ int vq3d_preact_tiny_bwd(int32_t dtype, int32_t batch, int32_t channels, int32_t
     if (!x || !g || !w1 || !w2 || !w3 || !p || !gr || !saved || !workspace || !gx)
         return fail("preact_tiny_bwd: null pointer");
     hipStream_t s = as_stream(stream);
-    static bool attr = false;
-    if (!attr) {
-        allow_lds(k_tiny_bwd_a<h16_t>);
-        allow_lds(k_tiny_bwd_a<float>);
-        allow_lds(k_tiny_bwd_b<h16_t>);
-        allow_lds(k_tiny_bwd_b<float>);
-        attr = true;
-    }
+    opt_in_lds(k_tiny_bwd_a<h16_t>, kLdsMax);
+    opt_in_lds(k_tiny_bwd_a<float>, kLdsMax);
+    opt_in_lds(k_tiny_bwd_b<h16_t>, kLdsMax);
+    opt_in_lds(k_tiny_bwd_b<float>, kLdsMax);
     if (dtype == VQ3D_HALF) {
         k_tiny_bwd_a<h16_t><<<28, NTA, lds_a(a), s>>>(a, (const h16_t *)g, w2, w3, *p, *gr, saved, workspace);
         k_tiny_bwd_b<h16_t><<<1, NTB, lds_b(a), s>>>(a, (const h16_t *)x, (const h16_t *)g, w1, *p, *gr, saved,

@@ -47,12 +47,11 @@ __device__ __forceinline__ void ldv(const T *__restrict__ p, float (&o)[CV]) {
 template <typename T, int CV>
 __device__ __forceinline__ void stv(T *__restrict__ p, const float (&v)[CV]) {
     if constexpr (sizeof(T) == 2 && CV == 4) {
-        *reinterpret_cast<uint2 *>(p) = uint2{uint32_t(f2h(v[0])) | (uint32_t(f2h(v[1])) << 16),
-                                              uint32_t(f2h(v[2])) | (uint32_t(f2h(v[3])) << 16)};
+        *reinterpret_cast<uint2 *>(p) = uint2{pk2(v[0], v[1]), pk2(v[2], v[3])};
     } else if constexpr (sizeof(T) == 2 && CV == 8) {
         uint32_t q[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) q[j] = uint32_t(f2h(v[2 * j])) | (uint32_t(f2h(v[2 * j + 1])) << 16);
+        for (int j = 0; j < 4; ++j) q[j] = pk2(v[2 * j], v[2 * j + 1]);
         *reinterpret_cast<uint4 *>(p) = uint4{q[0], q[1], q[2], q[3]};
     } else {
 #pragma unroll
@@ -280,8 +279,8 @@ __global__ __launch_bounds__(256) void k_up2_bwd_run4(UArgs a, const h16_t *__re
                 if (addend) v += av;
                 v2[c] = v;
             }
-            res[s4 >> 1][2 * (s4 & 1)] = uint32_t(f2h(v2[0])) | (uint32_t(f2h(v2[1])) << 16);
-            res[s4 >> 1][2 * (s4 & 1) + 1] = uint32_t(f2h(v2[2])) | (uint32_t(f2h(v2[3])) << 16);
+            res[s4 >> 1][2 * (s4 & 1)] = pk2(v2[0], v2[1]);
+            res[s4 >> 1][2 * (s4 & 1) + 1] = pk2(v2[2], v2[3]);
         }
         *reinterpret_cast<u32x4 *>(gx + o) = res[0];
         *reinterpret_cast<u32x4 *>(gx + o + 8) = res[1];
@@ -411,8 +410,8 @@ __global__ __launch_bounds__(256) void k_up2_bwd_quad(UArgs a, const h16_t *__re
                         if (addend) v += av;
                         v2[c] = v;
                     }
-                    res[s4 >> 1][2 * (s4 & 1)] = uint32_t(f2h(v2[0])) | (uint32_t(f2h(v2[1])) << 16);
-                    res[s4 >> 1][2 * (s4 & 1) + 1] = uint32_t(f2h(v2[2])) | (uint32_t(f2h(v2[3])) << 16);
+                    res[s4 >> 1][2 * (s4 & 1)] = pk2(v2[0], v2[1]);
+                    res[s4 >> 1][2 * (s4 & 1) + 1] = pk2(v2[2], v2[3]);
                 }
                 *reinterpret_cast<u32x4 *>(gx + o) = res[0];
                 *reinterpret_cast<u32x4 *>(gx + o + 8) = res[1];

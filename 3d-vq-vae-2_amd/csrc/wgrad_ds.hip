@@ -23,7 +23,9 @@
 // branch conv at 512^2 x 128 (generic engine 779 us), the down blocks' 4x4x4 stride-2 branch convs
 // 4 -> 4 (512^2 -> 256^2), 8 -> 8 (256^2), 16 -> 16 (128^2; 619 us) and their 2x2x2 stride-2 skip
 // convs 4 -> 8, 8 -> 16 (zero padding, + bias1c prologue, bias1d gradient).
+#include "block_util.h"
 #include "engines.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -31,7 +33,6 @@ namespace vq3d {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
@@ -77,7 +78,6 @@ struct WArgs {
     const float *pro_a, *pro_b;
 };
 
-__device__ __forceinline__ int wrapm(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
 
 __device__ __forceinline__ hx8 tr8(const h16_t *p0, const h16_t *p1) {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p0));
@@ -88,7 +88,7 @@ __device__ __forceinline__ hx8 tr8(const h16_t *p0, const h16_t *p1) {
 // the prologue over 2 packed bf16 (zero padding stays zero: only loaded words come here)
 __device__ __forceinline__ uint32_t pro2(uint32_t w, const Prologue &pro) {
     const float lo = pro.apply(h2f_lo(w)), hi = pro.apply(h2f_hi(w));
-    return uint32_t(f2h(lo)) | (uint32_t(f2h(hi)) << 16);
+    return pk2(lo, hi);
 }
 
 template <int CI, int CO, int KS, int ST, int PAD, int DO, int TH, int TW>
@@ -326,17 +326,6 @@ const Inst *find_inst(const vq3d_conv_desc *d) {
     return nullptr;
 }
 
-int n_cu() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-        (void)hipGetLastError();
-    }
-    return n;
-}
-
 int nwg_of(const vq3d_conv_desc *d, const Inst &in) {
     const int ntiles = d->batch * (d->out_h / in.ntiles_h) * (d->out_w / in.ntiles_w);
     // <= 2 resident workgroups per CU; partial rows capped at ~8 MB (the 16 -> 16 conv has 16,384
@@ -358,15 +347,7 @@ int wgrad_ds(const vq3d_conv_desc *d, const void *x, const void *g, const float 
              float *dbias, void *ws, size_t ws_bytes, hipStream_t s) {
     const Inst *in = find_inst(d);
     if (!in || !ws || ws_bytes < wgrad_ds_ws(d)) return fail("conv(wgrad_ds): unsupported");
-    static const void *attr_done[8] = {};
-    for (int i = 0; i < 8; ++i) {
-        if (attr_done[i] == in->kern) break;
-        if (!attr_done[i]) {
-            (void)hipFuncSetAttribute(in->kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(in->lds));
-            attr_done[i] = in->kern;
-            break;
-        }
-    }
+    opt_in_lds(in->kern, in->lds);
     WArgs a;
     a.B = d->batch;
     a.Ho = d->out_h;
