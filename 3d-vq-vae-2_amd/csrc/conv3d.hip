@@ -25,7 +25,6 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "conv_mfma.inc"
@@ -308,15 +307,17 @@ static int pick_tile(int c) {
     return 16;
 }
 
+static int next_smaller_tile(int t) {
+    int smaller = 1;
+    for (int o : kTiles)
+        if (o < t) smaller = o;
+    return smaller;
+}
+
 // shrink the channel tile while the grid would leave the chip idle (tiny top-level grids)
 static int pick_tile_for(int c, int64_t work_items, int64_t target = 65536) {
     int t = pick_tile(c);
-    while (t > 1 && work_items * ((c + t - 1) / t) < target) {
-        int smaller = 1;
-        for (int o : kTiles)
-            if (o < t) smaller = o;
-        t = smaller;
-    }
+    while (t > 1 && work_items * ((c + t - 1) / t) < target) t = next_smaller_tile(t);
     return t;
 }
 
@@ -383,24 +384,85 @@ static BwdEpi<T> make_bwd_epi(const vq3d_dgrad_epilogue *epi, int pro_kind, cons
     return e;
 }
 
-static bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// ---------------------------------------------------------------------------- route
+// The one place where a conv's engine is chosen: the launch_* functions switch on the route of their
+// call, and vq3d_conv3d_workspace_size is the largest `bytes` over the call variants of a pass, so the
+// caller's scratch fits the engine that runs.  Inputs: the engines' own applicability / size functions.
+enum class Engine {
+    pointwise, tc, small, lines, mfma, s2, valu,  // forward and backward-data
+    pw_wgrad, tc_wgrad, mid_w2grad, wgrad_ds, lines_wgrad, gen_mfma, gen_tiled, valu_wgrad
+};
+static const char *const kEngineNames[] = {"pointwise", "tc", "small", "lines", "mfma", "s2", "valu",
+                                           "pw_wgrad", "tc_wgrad", "mid_w2grad", "wgrad_ds", "lines_wgrad",
+                                           "gen_mfma", "gen_tiled", "valu_wgrad"};
+struct Route { Engine engine; size_t bytes; };  // bytes: the workspace the engine needs
+// the call-dependent bits the choice reads
+struct Call {
+    bool res_up2;                            // forward: the epilogue adds an upsampled residual
+    bool dw, escale, dscale, dbias, dcbias;  // weight pass: what the call passes
+};
+// the variants of each pass whose routes can differ (plain form first)
+static const Call kCallVariants[3][3] = {
+    {{false}, {true}, {true}},
+    {{}, {}, {}},
+    {{false, true}, {false, true, false, false, true}, {false, true, true, true, true, true}}};
 
-// small grids with many channels: reduction split over workgroups (conv_small.hip)
-static bool use_small(const vq3d_conv_desc *d, bool dgrad) {
-    if (!small_applicable(d, dgrad)) return false;
-    // measured: 9-20x faster than the lines / VALU engines at 128 voxels (8x8x2, 128 channels);
-    // from 1024 voxels on only where the lines engine cannot take the shape
+// the direct MFMA engine's plan for a pass (backward-data, stride 1 only: the forward conv of g
+// with the flipped, transposed kernel, no prologue)
+static MPlan mfma_plan(const vq3d_conv_desc *d, int pass, const float *pa = nullptr, const float *pb = nullptr) {
+    const int Ct = d->cin + d->cin2, circ = d->pad_mode == VQ3D_PAD_CIRCULAR, pp = d->kernel - 1 - d->pad;
+    const bool dgrad = pass == VQ3D_PASS_BWD_DATA;
+    if (dgrad && (d->stride != 1 || pp < 0)) return MPlan{};
+    MPlan m = dgrad ? plan_mfma(d->batch, d->cout, 0, Ct, d->out_h, d->out_w, d->out_d, d->in_h, d->in_w, d->in_d,
+                                d->kernel, 1, pp, circ)
+                    : plan_mfma(d->batch, d->cin, d->cin2, d->cout, d->in_h, d->in_w, d->in_d, d->out_h, d->out_w,
+                                d->out_d, d->kernel, d->stride, d->pad, circ, pass == VQ3D_PASS_BWD_WEIGHT);
+    m.a.pro_kind = dgrad ? int(VQ3D_PRO_NONE) : d->pro_kind;
+    m.a.pro_a = dgrad ? nullptr : pa;
+    m.a.pro_b = dgrad ? nullptr : pb;
+    m.a.wCt = Ct;
+    return m;
+}
+
+static Route route(const vq3d_conv_desc *d, int pass, const Call &c) {
+    const bool half = d->dtype == VQ3D_HALF;
+    if (pass == VQ3D_PASS_BWD_WEIGHT) {
+        if (is_pointwise(d)) return {Engine::pw_wgrad, pw_wgrad_workspace(d)};
+        if (tc_applicable(d)) return {Engine::tc_wgrad, tc_workspace(d, pass)};
+        if (!half) return {Engine::valu_wgrad, 0};
+        const bool plain = c.dw && !c.escale && !c.dscale && !c.dcbias;
+        if (mid_w2grad_ok(d) && plain && !c.dbias) return {Engine::mid_w2grad, mid_w2grad_ws(d)};
+        if (wgrad_ds_ok(d) && plain) return {Engine::wgrad_ds, wgrad_ds_ws(d)};
+        // the lines engine for wide inputs (>= 32 channels: 36 -> 36 at 32x32x8 runs 4.7x faster than
+        // the direct MFMA engine) or where the direct engine does not apply; the direct engine for the
+        // few-channel large grids, where it is measured faster (9 -> 9 at 128^2 x 32 on par, 4 -> 4 at
+        // 256^2 x 64 1.9x).  Sending small wide grids to the direct engine was measured and left off.
+        const MPlan m = mfma_plan(d, pass);
+        if (lines_wgrad_applicable(d) && (d->cin + d->cin2 >= 32 || !m.ok))
+            return {Engine::lines_wgrad, lines_wgrad_workspace(d)};
+        if (!m.ok) return {Engine::valu_wgrad, 0};
+        // the MFMA kernel holds up to 4 tiles of 16 outputs; wider ones stay on the VALU tiled kernel (64-channel
+        // MFMA chunks measured slower: 57 vs 48.7 us at 128 -> 128 @8x8x2, 212 vs 155 us at 64 -> 128 k4 s2 @32x32x8)
+        return {d->cout <= 64 ? Engine::gen_mfma : Engine::gen_tiled, gen_wgrad_bytes(gen_wgrad_geom(m), d->cout)};
+    }
+    const bool dgrad = pass == VQ3D_PASS_BWD_DATA;
+    if (is_pointwise(d)) return {Engine::pointwise, dgrad ? pw_dgrad_workspace(d) : 0};
+    if (tc_applicable(d) && !c.res_up2) return {Engine::tc, tc_workspace(d, pass)};
+    // small grids with many channels: reduction split over workgroups (conv_small.hip).  Measured
+    // 9-20x faster than the lines / VALU engines at 128 voxels (8x8x2, 128 channels); above 512
+    // voxels only where neither the lines engine nor the parity-tap engine (measured 2x faster
+    // there) takes the shape.  Its matrix-core form above 512 voxels was measured and left off.
     const int64_t nv = dgrad ? int64_t(d->batch) * d->in_h * d->in_w * d->in_d
                              : int64_t(d->batch) * d->out_h * d->out_w * d->out_d;
-    if (nv <= 512) return true;
-    // matrix-core form up to VQ3D_SMALL_MMA_MAX voxels (default 512: the lines engine above)
-    static const int64_t mma_max = [] {
-        const char *e = std::getenv("VQ3D_SMALL_MMA_MAX");
-        return e ? std::atoll(e) : int64_t(512);
-    }();
-    if (nv <= mma_max && small_mma_form(d, dgrad)) return true;
-    if (dgrad && dgrad_s2_applicable(d)) return false;  // parity-tap engine measured 2x faster there
-    return !lines_applicable(d, dgrad);
+    if (small_applicable(d, dgrad) &&
+        (nv <= 512 || !((dgrad && dgrad_s2_applicable(d)) || lines_applicable(d, dgrad))))
+        return {Engine::small, small_workspace(d, dgrad)};
+    if (half) {
+        if (lines_applicable(d, dgrad)) return {Engine::lines, lines_workspace(d, dgrad)};
+        if (mfma_plan(d, pass).ok) return {Engine::mfma, 0};
+    }
+    if (dgrad && dgrad_s2_applicable(d)) return {Engine::s2, 0};
+    return {Engine::valu, 0};
 }
 
 template <typename T>
@@ -413,39 +475,29 @@ static int launch_fwd(const vq3d_conv_desc *d, const void *x, const void *x2, co
     if (fe.res && fe.res_up2 && ((d->out_h | d->out_w | d->out_d) & 1))
         return fail("conv: residual_up2 needs even output");
     if (fe.act == VQ3D_ACT_ELU_AFFINE && (!fe.act_a || !fe.act_b)) return fail("conv: ELU_AFFINE needs act_a/b");
-    if (is_pointwise(d)) {
-        BwdEpi<T> be = {};
+    const BwdEpi<T> be = {};
+    const Engine engine = route(d, VQ3D_PASS_FWD, Call{fe.res && fe.res_up2}).engine;
+    switch (engine) {
+    case Engine::pointwise:
         return launch_pw1<T>(d, false, x, x2, w, pa, pb, fe, be, nullptr, y, nullptr, nullptr, nullptr, ws, ws_bytes,
                              s);
-    }
-    if (tc_applicable(d) && !(fe.res && fe.res_up2)) {
-        BwdEpi<T> be = {};
+    case Engine::tc:
         return launch_tc<T>(d, false, x, w, pa, pb, fe, be, nullptr, y, nullptr, nullptr, ws, ws_bytes, s);
-    }
-    if (use_small(d, false)) {
-        BwdEpi<T> be = {};
+    case Engine::small:
         return launch_small<T>(d, false, x, x2, w, pa, pb, fe, be, nullptr, y, nullptr, nullptr, nullptr, ws, ws_bytes,
                                s);
-    }
-    if constexpr (std::is_same<T, h16_t>::value) {
-        if (lines_applicable(d, false)) {
-            BwdEpi<T> be = {};
-            return launch_lines(d, false, x, x2, w, pa, pb, fe, be, nullptr, y, nullptr, nullptr, nullptr, ws,
-                                ws_bytes, s);
+    case Engine::lines:
+    case Engine::mfma:  // 16-bit only
+        if constexpr (std::is_same<T, h16_t>::value) {
+            if (engine == Engine::lines)
+                return launch_lines(d, false, x, x2, w, pa, pb, fe, be, nullptr, y, nullptr, nullptr, nullptr, ws,
+                                    ws_bytes, s);
+            return launch_mfma<false>(mfma_plan(d, VQ3D_PASS_FWD, pa, pb), (const T *)x, (const T *)x2, w, fe, be, 0,
+                                      nullptr, (T *)y, nullptr, nullptr, nullptr, s);
         }
-        {
-            MPlan m = plan_mfma(d->batch, d->cin, d->cin2, d->cout, d->in_h, d->in_w, d->in_d, d->out_h, d->out_w,
-                                d->out_d, d->kernel, d->stride, d->pad, d->pad_mode == VQ3D_PAD_CIRCULAR);
-            if (m.ok) {
-                m.a.pro_kind = d->pro_kind;
-                m.a.pro_a = pa;
-                m.a.pro_b = pb;
-                m.a.wCt = d->cin + d->cin2;
-                BwdEpi<T> be = {};
-                return launch_mfma<false>(m, (const T *)x, (const T *)x2, w, fe, be, 0, nullptr, (T *)y, nullptr,
-                                          nullptr, nullptr, s);
-            }
-        }
+        break;
+    default:  // Engine::valu
+        break;
     }
     const int cot = pick_tile_for(d->cout, nvox);
     const int Ct = d->cin + d->cin2, K3 = d->kernel * d->kernel * d->kernel;
@@ -471,41 +523,32 @@ static int launch_dgrad(const vq3d_conv_desc *d, const void *g, const float *gsc
     const int64_t nvox = int64_t(d->batch) * d->in_h * d->in_w * d->in_d;
     const int cit = pick_tile_for(Ct, nvox);
     BwdEpi<T> be = make_bwd_epi<T>(epi, d->pro_kind, pa);
-    if (is_pointwise(d)) {
-        FwdEpi<T> fe = {};
+    const FwdEpi<T> fe = {};
+    const Engine engine = route(d, VQ3D_PASS_BWD_DATA, Call{}).engine;
+    switch (engine) {
+    case Engine::pointwise:
         return launch_pw1<T>(d, true, g, nullptr, w, pa, nullptr, fe, be, gscale, gx, gx2, dpre, dpost, ws, ws_bytes,
                              s);
-    }
-    if (tc_applicable(d)) {
-        FwdEpi<T> fe = {};
+    case Engine::tc:
         return launch_tc<T>(d, true, g, w, pa, nullptr, fe, be, gscale, gx, dpre, dpost, ws, ws_bytes, s);
-    }
-    if (use_small(d, true)) {
-        FwdEpi<T> fe = {};
+    case Engine::small:
         return launch_small<T>(d, true, g, nullptr, w, pa, nullptr, fe, be, gscale, gx, gx2, dpre, dpost, ws, ws_bytes,
                                s);
-    }
-    if constexpr (std::is_same<T, h16_t>::value) {
-        // stride-1 backward-data == forward conv of g with the flipped, transposed kernel
-        if (lines_applicable(d, true)) {
-            FwdEpi<T> fe = {};
-            return launch_lines(d, true, g, nullptr, w, pa, nullptr, fe, be, gscale, gx, gx2, dpre, dpost, ws,
-                                ws_bytes, s);
+    case Engine::lines:
+    case Engine::mfma:  // 16-bit only
+        if constexpr (std::is_same<T, h16_t>::value) {
+            if (engine == Engine::lines)
+                return launch_lines(d, true, g, nullptr, w, pa, nullptr, fe, be, gscale, gx, gx2, dpre, dpost, ws,
+                                    ws_bytes, s);
+            return launch_mfma<true>(mfma_plan(d, VQ3D_PASS_BWD_DATA), (const T *)g, nullptr, w, fe, be, d->cin,
+                                     gscale, (T *)gx, (T *)gx2, dpre, dpost, s);
         }
-        if (d->stride == 1) {
-            const int pp = d->kernel - 1 - d->pad;
-            MPlan m = plan_mfma(d->batch, d->cout, 0, Ct, d->out_h, d->out_w, d->out_d, d->in_h, d->in_w, d->in_d,
-                                d->kernel, 1, pp, d->pad_mode == VQ3D_PAD_CIRCULAR);
-            if (m.ok && pp >= 0) {
-                m.a.pro_kind = VQ3D_PRO_NONE;
-                m.a.wCt = Ct;
-                FwdEpi<T> fe = {};
-                return launch_mfma<true>(m, (const T *)g, nullptr, w, fe, be, d->cin, gscale, (T *)gx, (T *)gx2,
-                                         dpre, dpost, s);
-            }
-        }
+        break;
+    case Engine::s2:
+        return launch_dgrad_s2<T>(d, g, gscale, w, be, gx, gx2, dpre, dpost, s);
+    default:  // Engine::valu
+        break;
     }
-    if (dgrad_s2_applicable(d)) return launch_dgrad_s2<T>(d, g, gscale, w, be, gx, gx2, dpre, dpost, s);
     const int K3 = d->kernel * d->kernel * d->kernel;
     const size_t all = size_t(K3) * d->cout * cit * 4;
     const int all_taps = all <= kAllTapsLds;
@@ -522,78 +565,34 @@ static int launch_dgrad(const vq3d_conv_desc *d, const void *g, const float *gsc
     return check_launch("conv3d_bwd_data");
 }
 
-// k^3 weight gradient engine choice (bf16): the lines engine for wide inputs (>= 32 channels:
-// 36 -> 36 at 32x32x8 runs 4.7x faster than the direct MFMA engine) or where the direct engine
-// does not apply; the direct engine for the few-channel large grids, where it is measured
-// faster (9 -> 9 at 128^2 x 32 on par, 4 -> 4 at 256^2 x 64 1.9x).
-static bool use_lines_wgrad(const vq3d_conv_desc *d) {
-    if (d->dtype != VQ3D_HALF || !lines_wgrad_applicable(d)) return false;
-    // grids up to VQ3D_WGRAD_MFMA_MAX output voxels go to the direct engine even when wide (A/B;
-    // default 0: the lines engine for every wide input)
-    static const int64_t mfma_max = [] {
-        const char *e = std::getenv("VQ3D_WGRAD_MFMA_MAX");
-        return e ? std::atoll(e) : int64_t(0);
-    }();
-    const int64_t nv = int64_t(d->batch) * d->out_h * d->out_w * d->out_d;
-    if (nv <= mfma_max && plan_mfma(d->batch, d->cin, d->cin2, d->cout, d->in_h, d->in_w, d->in_d, d->out_h, d->out_w,
-                                    d->out_d, d->kernel, d->stride, d->pad, d->pad_mode == VQ3D_PAD_CIRCULAR, true)
-                              .ok)
-        return false;
-    if (d->cin + d->cin2 >= 32) return true;
-    return !plan_mfma(d->batch, d->cin, d->cin2, d->cout, d->in_h, d->in_w, d->in_d, d->out_h, d->out_w, d->out_d,
-                      d->kernel, d->stride, d->pad, d->pad_mode == VQ3D_PAD_CIRCULAR, true)
-                .ok;
-}
-
-// the generic engines' image workspace (deterministic path; without it they fall back to atomics)
-static size_t generic_wgrad_ws(const vq3d_conv_desc *d) {
-    if (d->dtype != VQ3D_HALF || use_lines_wgrad(d) || d->kernel == 1) return 0;
-    MPlan m = plan_mfma(d->batch, d->cin, d->cin2, d->cout, d->in_h, d->in_w, d->in_d, d->out_h, d->out_w, d->out_d,
-                        d->kernel, d->stride, d->pad, d->pad_mode == VQ3D_PAD_CIRCULAR, true);
-    if (!m.ok) return 0;
-    m.a.wCt = d->cin + d->cin2;
-    return gen_wgrad_bytes(gen_wgrad_geom(m), d->cout);
-}
-
 template <typename T>
 static int launch_wgrad(const vq3d_conv_desc *d, const void *x, const void *x2, const void *g, const float *pa,
                         const float *pb, const float *w, const float *escale, float *dw, float *dscale, float *dbias,
                         float *dcbias, void *ws, size_t ws_bytes, hipStream_t s) {
     ConvArgs a = make_args(d, pa, pb);
-    const int Ct = d->cin + d->cin2;
-    const int K3 = d->kernel * d->kernel * d->kernel;
-    const int Kt = Ct * K3;
-    if (is_pointwise(d)) {
+    const int Kt = (d->cin + d->cin2) * d->kernel * d->kernel * d->kernel;
+    const Route r = route(d, VQ3D_PASS_BWD_WEIGHT, Call{false, dw != nullptr, escale != nullptr, dscale != nullptr,
+                                                        dbias != nullptr, dcbias != nullptr});
+    // the per-workgroup partials have to fit: no engine falls back to another path (or to atomics)
+    if (r.bytes && (!ws || ws_bytes < r.bytes)) return fail("conv3d_bwd_weight: workspace too small");
+    switch (r.engine) {
+    case Engine::pw_wgrad:
         return launch_pw_wgrad(d, x, x2, g, pa, pb, w, escale, dw, dscale, dbias, dcbias, ws, ws_bytes, s);
-    }
-    if (tc_applicable(d))
+    case Engine::tc_wgrad:
         return launch_tc_wgrad<T>(d, x, g, pa, pb, w, escale, dw, dscale, dbias, dcbias, ws, ws_bytes, s);
-    if constexpr (std::is_same<T, h16_t>::value) {
-        if (mid_w2grad_ok(d) && dw && !escale && !dscale && !dbias && !dcbias && ws && ws_bytes >= mid_w2grad_ws(d))
-            return mid_w2grad(d, x, g, dw, ws, ws_bytes, s);
-        if (wgrad_ds_ok(d) && dw && !escale && !dscale && !dcbias && ws && ws_bytes >= wgrad_ds_ws(d))
-            return wgrad_ds(d, x, g, pa, pb, dw, dbias, ws, ws_bytes, s);
-        if (use_lines_wgrad(d))
-            return launch_lines_wgrad(d, x, x2, g, pa, pb, w, escale, dw, dscale, dbias, dcbias, ws, ws_bytes, s);
-        {
-            MPlan m = plan_mfma(d->batch, d->cin, d->cin2, d->cout, d->in_h, d->in_w, d->in_d, d->out_h, d->out_w,
-                                d->out_d, d->kernel, d->stride, d->pad, d->pad_mode == VQ3D_PAD_CIRCULAR, true);
-            if (m.ok) {
-                m.a.pro_kind = d->pro_kind;
-                m.a.pro_a = pa;
-                m.a.pro_b = pb;
-                m.a.wCt = Ct;
-                // MFMA engine holds up to 4 tiles of 16 output channels; wider outputs (the top levels'
-                // 128-channel convs on 128..1,024 voxels) stay on the VALU tiled kernel: 64-channel
-                // chunks on the matrix cores measured slower there (r04f / r04g: 57 vs 48.7 us at
-                // 128 -> 128 @8x8x2, 212 vs 155 us at 64 -> 128 k4 s2 @32x32x8)
-                if (d->cout <= 64)
-                    return launch_wgrad_mfma(m, (const T *)x, (const T *)x2, (const T *)g, w, escale, dw, dscale,
-                                             dbias, dcbias, ws, ws_bytes, s);
-                return launch_wgrad_tiled(m, (const T *)x, (const T *)x2, (const T *)g, w, escale, dw, dscale,
-                                          dbias, dcbias, ws, ws_bytes, s);
-            }
-        }
+    case Engine::mid_w2grad:
+        return mid_w2grad(d, x, g, dw, ws, ws_bytes, s);
+    case Engine::wgrad_ds:
+        return wgrad_ds(d, x, g, pa, pb, dw, dbias, ws, ws_bytes, s);
+    case Engine::lines_wgrad:
+        return launch_lines_wgrad(d, x, x2, g, pa, pb, w, escale, dw, dscale, dbias, dcbias, ws, ws_bytes, s);
+    case Engine::gen_mfma:
+    case Engine::gen_tiled:  // 16-bit only
+        return (r.engine == Engine::gen_mfma ? launch_wgrad_mfma : launch_wgrad_tiled)(
+            mfma_plan(d, VQ3D_PASS_BWD_WEIGHT, pa, pb), (const h16_t *)x, (const h16_t *)x2, (const h16_t *)g, w,
+            escale, dw, dscale, dbias, dcbias, static_cast<float *>(ws), s);
+    default:  // Engine::valu_wgrad
+        break;
     }
     // rows per workgroup: all rows when they fit (voxel sub-streams fill the rest), else 256
     const int R = Kt >= 256 ? 256 : (Kt > 128 ? Kt : std::max(1, Kt));
@@ -603,12 +602,8 @@ static int launch_wgrad(const vq3d_conv_desc *d, const void *x, const void *x2, 
     const int64_t max_nbx = (nrows + min_rows - 1) / min_rows;
     // channel tile: shrink it while there are too few workgroups to fill the chip
     int cot = pick_tile(d->cout);
-    while (cot > 1 && int64_t(ytiles) * ((d->cout + cot - 1) / cot) * std::min<int64_t>(max_nbx, 2048) < 512) {
-        int smaller = 1;
-        for (int o : kTiles)
-            if (o < cot) smaller = o;
-        cot = smaller;
-    }
+    while (cot > 1 && int64_t(ytiles) * ((d->cout + cot - 1) / cot) * std::min<int64_t>(max_nbx, 2048) < 512)
+        cot = next_smaller_tile(cot);
     const int ztiles = (d->cout + cot - 1) / cot;
     const int64_t tiles = int64_t(ytiles) * ztiles;
     int64_t nbx = std::max<int64_t>(1, 1024 / tiles);  // x tiles: bounds the atomic traffic (nbx * E)
@@ -662,15 +657,15 @@ int vq3d_conv3d_bwd_data(const vq3d_conv_desc *d, const void *g, const float *gs
 }
 
 size_t vq3d_conv3d_workspace_size(const vq3d_conv_desc *d, int32_t pass) {
-    if (validate(d)) return 0;
-    if (tc_applicable(d)) return tc_workspace(d, pass);
-    if (pass != VQ3D_PASS_BWD_WEIGHT && !is_pointwise(d) && use_small(d, pass == VQ3D_PASS_BWD_DATA))
-        return small_workspace(d, pass == VQ3D_PASS_BWD_DATA);
-    if (pass == VQ3D_PASS_FWD) return lines_workspace(d, false);
-    if (pass == VQ3D_PASS_BWD_DATA) return is_pointwise(d) ? pw_dgrad_workspace(d) : lines_workspace(d, true);
-    if (is_pointwise(d)) return pw_wgrad_workspace(d);
-    return std::max({use_lines_wgrad(d) ? lines_wgrad_workspace(d) : size_t(0), mid_w2grad_ws(d), wgrad_ds_ws(d),
-                     generic_wgrad_ws(d)});
+    if (pass < VQ3D_PASS_FWD || pass > VQ3D_PASS_BWD_WEIGHT || validate(d)) return 0;
+    size_t bytes = 0;
+    for (const Call &c : kCallVariants[pass]) bytes = std::max(bytes, route(d, pass, c).bytes);
+    return bytes;
+}
+
+const char *vq3d_conv3d_engine(const vq3d_conv_desc *d, int32_t pass) {
+    if (pass < VQ3D_PASS_FWD || pass > VQ3D_PASS_BWD_WEIGHT || validate(d)) return "";
+    return kEngineNames[int(route(d, pass, kCallVariants[pass][0]).engine)];
 }
 
 int vq3d_conv3d_bwd_weight(const vq3d_conv_desc *d, const void *x, const void *x2, const void *g, const float *pro_a,

@@ -776,11 +776,12 @@ int launch_lines(const vq3d_conv_desc *d, bool dgrad, const void *x, const void 
         P.a.vec_out = P.a.vec_out && !fe.res_up2 && al(y) && (!fe.res || al(fe.res));
     }
     const int wCt = d->cin + d->cin2;
-    // pre-pack the weights once per call when the caller gave room (else each workgroup packs)
+    // pre-pack the weights once per call; small images are packed in-kernel, by each workgroup
     const uint4 *wpk = nullptr;
     const int items_per_wg = P.a.nks * 4 * P.a.ntn;
     const bool want_pack = items_per_wg > 2048;
-    if (want_pack && ws && ws_bytes >= ws_of(P)) {  // small images are packed in-kernel
+    if (want_pack && (!ws || ws_bytes < ws_of(P))) return fail("conv(lines): workspace too small");
+    if (want_pack) {
         const int items = P.a.nks * 4 * P.a.ntn;
         const dim3 pg{unsigned((items + 255) / 256), unsigned(P.a.ntg), 1u};
         if (dgrad) k_lines_pack<true><<<pg, 256, 0, s>>>(P.a, w, wCt, P.a.ntn, static_cast<uint4 *>(ws));

@@ -753,13 +753,14 @@ static int launch_wgrad_gen_reduce(const MPlan &m, const GenW &gw, const float *
     return check_launch("conv3d_bwd_weight(generic reduce)");
 }
 
+// part: the call's workspace, gen_wgrad_bytes long (conv3d.hip's launch_wgrad refuses a shorter one,
+// so the kernels' part == nullptr atomic branch is never taken from here)
 static int launch_wgrad_tiled(MPlan m, const h16_t *x, const h16_t *x2, const h16_t *g, const float *w,
-                              const float *escale, float *dw, float *dscale, float *dbias, float *dcbias, void *ws,
-                              size_t ws_bytes, hipStream_t s) {
+                              const float *escale, float *dw, float *dscale, float *dbias, float *dcbias,
+                              float *part, hipStream_t s) {
     const GenW gw = gen_wgrad_geom(m);
     const int ncog = gw.ncog, tpb = gw.tpb, S = gw.S, nbx = gw.nbx;
     const int nbricks = int(m.blocks);
-    float *part = ws && ws_bytes >= gen_wgrad_bytes(gw, m.a.N) ? static_cast<float *>(ws) : nullptr;
     dim3 grid((unsigned)nbx, (unsigned)gw.ytiles, (unsigned)gw.nchunks);
 #define WG(CP) k_wgrad_tiled<CP><<<grid, 256, m.lds, s>>>(m.a, x, x2, g, ncog, tpb, S, nbricks, w, escale, dw, dscale, dbias, dcbias, part)
     switch (m.cp) {
@@ -770,7 +771,7 @@ static int launch_wgrad_tiled(MPlan m, const h16_t *x, const h16_t *x2, const h1
     }
 #undef WG
     if (int r = check_launch("conv3d_bwd_weight(tiled)")) return r;
-    return part ? launch_wgrad_gen_reduce(m, gw, part, w, escale, dw, dscale, dbias, dcbias, s) : 0;
+    return launch_wgrad_gen_reduce(m, gw, part, w, escale, dw, dscale, dbias, dcbias, s);
 }
 
 
@@ -971,13 +972,12 @@ __global__ __launch_bounds__(256) void k_wgrad_mfma(MArgs a, const h16_t *__rest
 }
 
 static int launch_wgrad_mfma(MPlan m, const h16_t *x, const h16_t *x2, const h16_t *g, const float *w,
-                             const float *escale, float *dw, float *dscale, float *dbias, float *dcbias, void *ws,
-                             size_t ws_bytes, hipStream_t s) {
+                             const float *escale, float *dw, float *dscale, float *dbias, float *dcbias,
+                             float *part, hipStream_t s) {
     const MArgs &a = m.a;
     const GenW gw = gen_wgrad_geom(m);
     const int ntm = gw.ntm, NPW = gw.npw;
     const int nbricks = int(m.blocks);
-    float *part = ws && ws_bytes >= gen_wgrad_bytes(gw, a.N) ? static_cast<float *>(ws) : nullptr;
     const int lds_image = size_t(a.N) * 64 * NPW * 4 <= m.lds ? 1 : 0;
     dim3 grid((unsigned)gw.nbx, (unsigned)gw.ytiles, (unsigned)gw.nchunks);
 #define WGM(CP, NTM, NPW_)                                                                                      \
@@ -1006,7 +1006,7 @@ static int launch_wgrad_mfma(MPlan m, const h16_t *x, const h16_t *x2, const h16
 #undef NPWS7
 #undef WGM
     if (int r = check_launch("conv3d_bwd_weight(mfma)")) return r;
-    return part ? launch_wgrad_gen_reduce(m, gw, part, w, escale, dw, dscale, dbias, dcbias, s) : 0;
+    return launch_wgrad_gen_reduce(m, gw, part, w, escale, dw, dscale, dbias, dcbias, s);
 }
 
 }  // namespace vq3d

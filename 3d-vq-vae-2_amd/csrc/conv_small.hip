@@ -364,10 +364,6 @@ bool small_applicable(const vq3d_conv_desc *d, bool dgrad) {
     return size_t(d->kernel) * d->kernel * d->kernel * 4 * OT * 4 <= kSmallLds;
 }
 
-bool small_mma_form(const vq3d_conv_desc *d, bool dgrad) {
-    return small_applicable(d, dgrad) && plan_small(d, dgrad, nullptr, nullptr).mma;
-}
-
 // partial rows of either form: a matrix-core plan falls back to k_small (its own, possibly
 // larger, split) when an operand is not 16-byte aligned, so the workspace covers both
 static size_t small_partials_bytes(const SPlan &p) {

@@ -848,8 +848,8 @@ int launch_pw_wgrad(const vq3d_conv_desc *d, const void *x, const void *x2, cons
     WmArgs m;
     int mpw, ntt, mbx;
     size_t mlds;
-    const bool mma = !(reg_path(d) && a.vec) && plan_mma(d, x, x2, g, m, mpw, ntt, mbx, mlds) &&
-                     size_t(mbx) * m.N * (m.Ct + 1) * 4 <= ws_bytes;
+    const bool mma = !(reg_path(d) && a.vec) && plan_mma(d, x, x2, g, m, mpw, ntt, mbx, mlds);
+    if (mma && size_t(mbx) * m.N * (m.Ct + 1) * 4 > ws_bytes) return fail("conv3d_bwd_weight: workspace too small");
     if (mma) {
         nbx = mbx;
         a.ne = m.N * (m.Ct + 1);

@@ -53,6 +53,7 @@ class DgradEpilogue(ctypes.Structure):
 
 _SIGS = {
     "vq3d_conv3d_workspace_size": (c_size, [P, c_int]),
+    "vq3d_conv3d_engine": (ctypes.c_char_p, [P, c_int]),
     "vq3d_conv3d_fwd": (c_int, [P, P, P, P, P, P, P, P, P, c_size, P]),
     "vq3d_conv3d_bwd_data": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_size, P]),
     "vq3d_conv3d_bwd_weight": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, c_size, P]),

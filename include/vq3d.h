@@ -85,10 +85,18 @@ typedef struct vq3d_dgrad_epilogue {
 /* --- 3-D convolution (replaces nn.Conv3d / F.pad circular, layers.py:124-171,535,377,490,508) ---
  * Every conv entry point takes a caller-owned scratch `workspace` of at least
  * vq3d_conv3d_workspace_size(d, pass) bytes (may be 0 -> NULL allowed): packed bf16 weight
- * fragments for the k^3 MFMA engine, per-workgroup partials for the weight gradient.  Its
- * contents are scratch; it must stay allocated until the launches on `stream` complete. */
+ * fragments for the k^3 MFMA engine, per-workgroup partials for the weight gradient.  The size
+ * covers every form of the pass's call (any epilogue, any set of gradients).  A workspace that is
+ * NULL or shorter than the engine of the call needs is an error ("workspace too small"): no
+ * engine falls back to another path.  Its contents are scratch; it must stay allocated until the
+ * launches on `stream` complete. */
 enum { VQ3D_PASS_FWD = 0, VQ3D_PASS_BWD_DATA = 1, VQ3D_PASS_BWD_WEIGHT = 2 };
 size_t vq3d_conv3d_workspace_size(const vq3d_conv_desc *d, int32_t pass);
+/* Host-only: the name of the engine a call of that pass takes in its plain form (forward without
+ * an upsampled residual, a weight pass that wants dw only); "" for an invalid descriptor or pass.
+ * Forward / backward-data: pointwise, tc, small, lines, mfma, s2, valu; weight pass: pw_wgrad,
+ * tc_wgrad, mid_w2grad, wgrad_ds, lines_wgrad, gen_mfma, gen_tiled, valu_wgrad. */
+const char *vq3d_conv3d_engine(const vq3d_conv_desc *d, int32_t pass);
 
 int vq3d_conv3d_fwd(const vq3d_conv_desc *d, const void *x, const void *x2, const float *w,
                     const float *pro_a, const float *pro_b, const vq3d_conv_epilogue *epi,
@@ -111,10 +119,11 @@ int vq3d_conv3d_bwd_data(const vq3d_conv_desc *d, const void *g, const float *gs
  *   dscale += sum(W * G)     (epilogue `scale`; needs w and epi_scale)
  *   dbias  += sum(g)         (epilogue scalar bias)
  *   dcbias += sum_v g[v,co]  (nn.Conv3d bias)
- * The workspace holds per-workgroup partials that a second kernel sums in a fixed order
- * (1x1x1 convs and the lines k^3 engine: deterministic); the direct k^3 engine used for
- * few-channel large grids accumulates with fp32 atomics, so its last bits are
- * order-dependent like cuDNN's wgrad. */
+ * Every 16-bit engine writes per-workgroup partials (or images) into the workspace and a
+ * second kernel sums them in a fixed order, so the 16-bit weight pass is deterministic bit for
+ * bit; a workspace too small for them is an error, never a switch to atomics.  Only the fp32
+ * direct k^3 engine (the exact-parity path) accumulates with fp32 atomics, so its last bits
+ * are order-dependent like cuDNN's wgrad. */
 int vq3d_conv3d_bwd_weight(const vq3d_conv_desc *d, const void *x, const void *x2, const void *g,
                            const float *pro_a, const float *pro_b, const float *w, const float *epi_scale,
                            float *dw, float *dscale, float *dbias, float *dcbias, void *workspace,

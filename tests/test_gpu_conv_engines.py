@@ -30,7 +30,8 @@ CASES = [
     (18, 9, (8, 8, 8), 1, 1, 0, False),
     (9, 2, (8, 8, 5), 1, 1, 0, False),
     (64, 128, (4, 4, 2), 1, 1, 0, False),
-    # channel counts that are not multiples of 4 (lines weight gradient, vector-run staging)
+    # channel counts that are not multiples of 4 (generic MFMA / tiny-channel weight gradient,
+    # vector-run staging): ODD_CASES
     (9, 9, (16, 16, 32), 3, 1, 1, True),
     (1, 1, (16, 8, 32), 3, 1, 1, True),
     (2, 2, (8, 8, 40), 3, 1, 1, True),
@@ -48,6 +49,18 @@ CASES = [
     (8, 8, (16, 16, 16), 4, 2, 1, False),
     (4, 4, (8, 8, 6), 3, 1, 1, True),
 ]
+ODD_CASES = CASES[18:23]
+DSHIFT_CASES = CASES[23:]
+FWD, DGRAD, WGRAD = 0, 1, 2
+
+
+def engine(dt, batch, cin, cin2, cout, hwd, geom, pass_, pro=0):
+    """vq3d_conv3d_engine: the engine a call with that descriptor takes in its plain form"""
+    import ctypes
+    from vq3d import _lib as L
+    from vq3d import ops
+    desc, _ = ops.conv_desc(dt, batch, cin, cin2, cout, *hwd, geom, pro)
+    return L.query("vq3d_conv3d_engine", ctypes.byref(desc), pass_).decode()
 
 
 HALF = [torch.bfloat16, torch.float16]  # the two 16-bit builds of the kernels
@@ -82,6 +95,8 @@ def test_mfma_forward_and_dgrad_match_valu(gpu, case, half):
     wt = rnd((cout, cin, k, k, k), gpu, g, 0.3)
     a = rnd((1,), gpu, g, 0.1)
     b = rnd((1,), gpu, g, 0.1)
+    if case in DSHIFT_CASES:
+        assert engine(half, 2, cin, 0, cout, (h, w, d), geom, FWD, 2) == "lines"
     ref = ops.conv_fwd(x, wt, geom, pro=(a, b), act=(b, a))
     out = ops.conv_fwd(x.to(_H[0]), wt, geom, pro=(a, b), act=(b, a))
     assert rel(out.float(), ref) < 1.5e-2, ("fwd", case, rel(out.float(), ref))
@@ -121,8 +136,8 @@ def test_mfma_dual_input_and_residual(gpu, half):
     assert rel(out.float(), ref) < 1.5e-2
 
 
-# more than 64 output channels: the MFMA weight gradient in 64-channel chunks (the top level's
-# stride-2 down convs and 128-channel branch convs), incl. a partial last chunk
+# more than 64 output channels: the LDS-tiled generic weight gradient (gen_tiled; the top level's
+# stride-2 down convs and 128-channel branch convs), incl. a partial last group of 8 outputs
 WGRAD_WIDE = [
     (64, 128, (8, 8, 4), 4, 2, 1, True),
     (128, 128, (8, 8, 4), 4, 2, 1, True),
@@ -148,6 +163,10 @@ def test_tiled_wgrad_matches_valu(gpu, case, half):
     sc = rnd((1,), gpu, g)
     oh, ow, od = geom.out(h), geom.out(w), geom.out(d)
     gy = rnd((2, cout, oh, ow, od), gpu, g).contiguous(memory_format=CL)
+    if case in WGRAD_WIDE:
+        assert engine(half, 2, cin, 0, cout, (h, w, d), geom, WGRAD, 2) == "gen_tiled"
+    if case in ODD_CASES:
+        assert engine(half, 2, cin, 0, cout, (h, w, d), geom, WGRAD, 2) == ("tc_wgrad" if cin == 1 else "gen_mfma")
     outs = []
     for dt in (torch.float32, _H[0]):
         dw = torch.zeros_like(wt)
@@ -201,6 +220,7 @@ def test_dgrad_s2_matches_valu(gpu, case, half):
     gy = rnd((2, cout, geom.out(h), geom.out(w), geom.out(d)), gpu, g).contiguous(memory_format=CL)
     add = rnd((2, cin, h, w, d), gpu, g).contiguous(memory_format=CL)
     ab, gs = rnd((1,), gpu, g, 0.3), rnd((1,), gpu, g)
+    assert engine(half, 2, cin, 0, cout, (h, w, d), geom, DGRAD) == "s2"
     outs = []
     for dt in (torch.float32, _H[0]):
         pre, post = torch.zeros(1, device=gpu), torch.zeros(1, device=gpu)
@@ -244,6 +264,8 @@ def test_wgrad_dshift(gpu, case, half):
     wt = rnd((cout, cin, k, k, k), gpu, g, 0.3)
     base = rnd((cout, cin, k, k, k), gpu, g)
     b1c = rnd((1,), gpu, g, 0.1)
+    want = "gen_mfma" if case is WGRAD_DS_CASES[-1] else "wgrad_ds"  # the last: depth without an instance
+    assert engine(half, bsz, cin, 0, cout, (h, w, d), geom, WGRAD, 1 if pro else 0) == want
     outs = []
     for dt in (torch.float32, _H[0]):
         dw = base.clone()
@@ -302,6 +324,7 @@ def test_pointwise_wgrad_vs_torch(gpu, case, dt):
     G = torch.einsum("bchwd,bohwd->oc", xp.double(), gy.double())
     dw = torch.zeros_like(wt)
     dscale, dbias, dcb = torch.zeros(1, device=gpu), torch.zeros(1, device=gpu), torch.zeros(cout, device=gpu)
+    assert engine(dt, 2, cin, cin2, cout, (h, w, d), ops.ConvGeom(1), WGRAD, 2) == "pw_wgrad"
     ops.conv_bwd(gy.to(dt), x.to(dt), wt, ops.ConvGeom(1), pro=(a, b), x2=None if x2 is None else x2.to(dt),
                  want_gx=False, dw=dw, dscale=dscale, dbias=dbias, dcbias=dcb, escale=sc)
     tol = 1e-4 if dt == torch.float32 else 1.5e-2
@@ -387,3 +410,57 @@ def test_pointwise_rows_residual_up2(gpu, case, dt):
     out = ops.conv_fwd(x.to(dt), wt, ops.ConvGeom(1), scale=sc, bias=bi, residual=res.to(dt), residual_up2=True)
     tol = 1e-5 if dt == torch.float32 else 1e-2
     assert rel(out.float(), ref.float()) < tol, rel(out.float(), ref.float())
+
+
+SHORT_WS_CASES = [
+    # (cin, cout, (h, w, d), k, pass, engine): routes whose engine keeps something in the workspace
+    (4, 4, (8, 8, 64), 3, WGRAD, "gen_mfma"),
+    (9, 9, (16, 16, 16), 3, WGRAD, "mid_w2grad"),
+    (18, 9, (16, 16, 16), 1, WGRAD, "pw_wgrad"),
+    (36, 36, (32, 32, 8), 3, FWD, "lines"),  # more than 2048 packed items per workgroup: pre-packed weights
+]
+
+
+@pytest.mark.parametrize("case", SHORT_WS_CASES)
+def test_short_workspace_is_refused(gpu, case):
+    """Once the route has chosen an engine, a missing workspace is an error: no other engine, no
+    per-workgroup packing, no atomics.  With exactly vq3d_conv3d_workspace_size bytes the call
+    succeeds, stays inside them (0xFF tail untouched) and equals the same call made through ops."""
+    import ctypes
+    from vq3d import _lib as L
+    from vq3d import ops
+    cin, cout, (h, w, d), k, pass_, eng = case
+    dt = torch.bfloat16
+    geom = ops.ConvGeom(k, 1, k // 2, k > 1)
+    assert engine(dt, 1, cin, 0, cout, (h, w, d), geom, pass_) == eng
+    desc, _ = ops.conv_desc(dt, 1, cin, 0, cout, h, w, d, geom, L.PRO_NONE)
+    nws = int(L.query("vq3d_conv3d_workspace_size", ctypes.byref(desc), pass_))
+    assert nws > 0
+    g = torch.Generator(device=gpu).manual_seed(17 + cin)
+    x = rnd((1, cin, h, w, d), gpu, g).to(dt).contiguous(memory_format=CL)
+    gy = rnd((1, cout, h, w, d), gpu, g).to(dt).contiguous(memory_format=CL)
+    wt = rnd((cout, cin, k, k, k), gpu, g, 0.3)
+    out = torch.zeros_like(wt) if pass_ == WGRAD else torch.zeros_like(gy)
+    epi = L.ConvEpilogue(scale=None, bias=None, cbias=None, residual=None, residual_up2=0, act=L.ACT_NONE,
+                         act_a=None, act_b=None)
+
+    def call(ws, nbytes):
+        if pass_ == WGRAD:
+            return L.query("vq3d_conv3d_bwd_weight", ctypes.byref(desc), L.ptr(x), None, L.ptr(gy), None, None,
+                           L.ptr(wt), None, L.ptr(out), None, None, None, ws, nbytes, L.stream())
+        return L.query("vq3d_conv3d_fwd", ctypes.byref(desc), L.ptr(x), None, L.ptr(wt), None, None,
+                       ctypes.byref(epi), L.ptr(out), ws, nbytes, L.stream())
+
+    assert call(None, 0) < 0
+    assert b"workspace" in L.load().vq3d_last_error()
+    tail = 4096
+    ws = torch.full((nws + tail,), 0xFF, dtype=torch.uint8, device=gpu)
+    assert call(ws.data_ptr(), nws) == 0, L.load().vq3d_last_error()
+    torch.cuda.synchronize()
+    assert bool((ws[nws:] == 0xFF).all()), "the launch wrote past the queried workspace"
+    if pass_ == WGRAD:
+        ref = torch.zeros_like(wt)
+        ops.conv_bwd(gy, x, wt, geom, want_gx=False, dw=ref)
+    else:
+        ref = ops.conv_fwd(x, wt, geom)
+    assert torch.equal(out, ref)

@@ -47,9 +47,10 @@ def test_small_grid_conv_vs_torch(gpu, case, dt):
     from vq3d import ops
     from vq3d import _lib as L
     cin, cout, (h, w, d), k, s, p, circ, cin2 = case
-    desc, _ = ops.conv_desc(torch.float32, 1, cin, cin2, cout, h, w, d, ops.ConvGeom(k, s, p, circ), 0)
-    assert L.query("vq3d_conv3d_workspace_size", ctypes.byref(desc), L.PASS_FWD) > 0, "small-grid engine not selected"
     tdt = torch.float32 if dt == "fp32" else torch.bfloat16
+    desc, _ = ops.conv_desc(tdt, 1, cin, cin2, cout, h, w, d, ops.ConvGeom(k, s, p, circ), L.PRO_ELU_ADD)
+    assert L.query("vq3d_conv3d_engine", ctypes.byref(desc), L.PASS_FWD) == b"small"
+    assert L.query("vq3d_conv3d_workspace_size", ctypes.byref(desc), L.PASS_FWD) > 0
     tol = 1e-4 if dt == "fp32" else 1.5e-2
     g = torch.Generator().manual_seed(cin * 7 + cout)
 

@@ -1,5 +1,5 @@
 # bench.py step time under environment settings, each run twice in alternation:
-#   gpurun -- bash tools/gpu_env_ab.sh "" "VQ3D_SMALL_MMA_MAX=4096" ...
+#   bash tools/gpu_env_ab.sh "" "VQ3D_W2_CHUNKS=4" ...
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" && mkdir -p gpurun_out
 for rep in 1 2; do
   i=0
