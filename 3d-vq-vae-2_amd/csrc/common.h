@@ -216,6 +216,15 @@ __device__ __forceinline__ Prologue make_prologue(int kind, const float *a, cons
     return p;
 }
 
+// ---------------------------------------------------------------- centre cylinder
+// (h, w) inside ExtractCenterCylinder's mask (load_nrrd_dataset.py:258-300): the loss and the
+// validation metrics count the same voxels
+__device__ __forceinline__ bool in_cylinder(int h, int w, int H, int W) {
+    // dist((h,w), (H/2, W/2)) <= min(H,W)/2  <=>  (2h-H)^2 + (2w-W)^2 <= min(H,W)^2 (exact)
+    const int64_t a = 2 * h - H, b = 2 * w - W, m = min(H, W);
+    return a * a + b * b <= m * m;
+}
+
 // ---------------------------------------------------------------- XCD-aware tile schedules
 // The dispatcher places workgroup b on XCD b % 8 and every XCD has its own L2.  With a grid that
 // is a multiple of 8, a persistent kernel gives each XCD a contiguous eighth of the tiles, and

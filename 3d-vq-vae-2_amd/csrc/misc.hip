@@ -71,12 +71,6 @@ static unsigned grid_for(int64_t n) { return unsigned(std::max<int64_t>(1, std::
 static bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ============================================================================ reconstruction loss
-__device__ __forceinline__ bool in_cylinder(int h, int w, int H, int W) {
-    // dist((h,w), (H/2, W/2)) <= min(H,W)/2  <=>  (2h-H)^2 + (2w-W)^2 <= min(H,W)^2 (exact)
-    const int64_t a = 2 * h - H, b = 2 * w - W, m = min(H, W);
-    return a * a + b * b <= m * m;
-}
-
 __device__ __forceinline__ float huber(float d) {
     const float ad = fabsf(d);
     return ad < 1.f ? 0.5f * d * d : ad - 0.5f;

@@ -5,7 +5,8 @@ from .layers import (Conv3d, Decoder, DownBlock, Encoder2, EvonormResBlock, Fixu
                      PreActFixupResBlock, PreQuantizationConditioning, Quantizer, ResizeConv3D, UpBlock)
 from .evonorm import EvoNorm3DS0  # noqa: F401
 from .model import VQVAE, default_args  # noqa: F401
+from .metrics import SSIM3DSlices, SliceMetrics, nmse, psnr, slice_metrics  # noqa: F401
 
 __all__ = ["VQVAE", "default_args", "Encoder2", "Decoder", "PreActFixupResBlock", "FixupResBlock",
            "EvonormResBlock", "Quantizer", "ResizeConv3D", "EvoNorm3DS0", "DownBlock", "UpBlock",
-           "PreQuantizationConditioning", "Conv3d"]
+           "PreQuantizationConditioning", "Conv3d", "slice_metrics", "SliceMetrics", "SSIM3DSlices", "nmse", "psnr"]

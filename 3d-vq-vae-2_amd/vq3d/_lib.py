@@ -115,6 +115,8 @@ _SIGS = {
     "vq3d_recon_loss_fwd": (c_int, [c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P]),
     "vq3d_recon_loss_bwd": (c_int, [c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "vq3d_cylinder_count": (c_i64, [c_int, c_int]),
+    "vq3d_slice_metrics_workspace_size": (c_size, [c_int] * 4),
+    "vq3d_slice_metrics": (c_int, [c_int, P, P, P] + [c_int] * 6 + [c_float] * 4 + [P, P, P, P]),
     "vq3d_evonorm_workspace_size": (c_size, [c_int, c_i64]),
     "vq3d_evonorm_fwd": (c_int, [c_int, P, c_int, c_i64, P, P, P, P, P, P, P]),
     "vq3d_evonorm_bwd": (c_int, [c_int, P, P, c_int, c_i64, P, P, P, P, P, P, P, P, P]),

@@ -14,6 +14,8 @@ vqvae/layers.py:134-171 nn.Conv3d, :685-728 the Quantizer, model.py:115-163 the 
     vq3d::parse_input / parse_input_backward  the fp32 volume into the 16-bit activation (layers.py:535)
     vq3d::upsample2x / upsample2x_backward    trilinear x2 (layers.py:591-597)
     vq3d::recon_loss / recon_loss_backward    smooth-L1 reconstruction + commitment sum (model.py:115-163)
+    vq3d::slice_metrics                       validation SSIM / NMSE / PSNR (model.py:20-30, 132-136;
+                                              no autograd: a metric, not a loss)
 
 Each operator runs exactly the kernels of the ctypes path (the same autograd.Function bodies of
 vq3d.functional, driven through a stand-in context), so `vq3d.functional.set_binding("library")`
@@ -535,6 +537,15 @@ def _loss_bwd(ctx, grads):
 _register("recon_loss", _loss_bwd, _loss_setup, (0, 4))
 
 
+@torch.library.custom_op("vq3d::slice_metrics", mutates_args=())
+def slice_metrics(pred: Tensor, target: Tensor, nvs: Tensor, elu: bool, cylinder: bool, data_range: float, k1: float,
+                  k2: float, psnr_range: float) -> List[Tensor]:
+    """[ssim_per_slice (B, D), stats (5,) = {ssim, mse, nmse, psnr, data_range_used}]; data_range <= 0:
+    computed from the batch (vq3d.metrics.slice_metrics is the public form)"""
+    from . import metrics
+    return list(metrics.slice_metrics_kernel(pred, target, nvs, elu, cylinder, data_range, k1, k2, psnr_range))
+
+
 def upsample(x):
     return _call("upsample2x", (x,), (x,))
 
@@ -647,6 +658,13 @@ def _recon_loss_fake(dec, x, nvs, cylinder, commit):
     return [s, torch.empty_like(s), _meta(dec, 3)]  # saves dec, x, nvs (inputs)
 
 
+@torch.library.register_fake("vq3d::slice_metrics")
+def _slice_metrics_fake(pred, target, nvs, elu, cylinder, data_range, k1, k2, psnr_range):
+    b, d = pred.shape[0], pred.shape[4]
+    return [torch.empty((b, d), dtype=torch.float32, device=pred.device),
+            torch.empty(5, dtype=torch.float32, device=pred.device)]
+
+
 for _n in ("conv3d_backward", "preact_block_backward", "preact_run_backward", "parse_input_backward",
            "recon_loss_backward"):
     torch.library.register_fake(f"vq3d::{_n}")(_eager_only(_n))
@@ -654,4 +672,4 @@ for _n in ("conv3d_backward", "preact_block_backward", "preact_run_backward", "p
 
 OPS = ("conv3d", "conv3d_backward", "preact_block", "preact_block_backward", "preact_run", "preact_run_backward",
        "vq_init", "vq_nearest", "vq_nearest_backward", "vq_ema", "parse_input", "parse_input_backward", "upsample2x",
-       "upsample2x_backward", "recon_loss", "recon_loss_backward")
+       "upsample2x_backward", "recon_loss", "recon_loss_backward", "slice_metrics")

@@ -19,6 +19,7 @@ from . import ops
 from . import parallel
 from .flat import FlatParams
 from .layers import Decoder, Encoder2, EvonormResBlock, FixupResBlock, PreActFixupResBlock
+from .metrics import slice_metrics
 from .optim import FusedAdam
 from .utils import booltype
 
@@ -143,13 +144,17 @@ class VQVAE(nn.Module):
 
     def shared_step(self, batch, batch_idx, mode='train'):
         assert mode in ('train', 'val')
-        loss, log_dict = self.recon_loss_f(batch, batch_idx)
+        loss, log_dict = self.recon_loss_f(batch, batch_idx, quality=(mode == 'val'))
         self.log_dict({f'{mode}_{key}': val for key, val in log_dict.items()}, logger=True)
         return loss
 
-    def loc_metric(self, batch, batch_idx) -> Tuple[torch.Tensor, dict]:
+    def loc_metric(self, batch, batch_idx, quality=False) -> Tuple[torch.Tensor, dict]:
         """elu -> pad-slice mask -> centre cylinder -> smooth-L1 mean + sum(commitment),
-        one fused kernel pair (model.py:115-160)."""
+        one fused kernel pair (model.py:115-160).  quality (validation only): also the slice-wise SSIM
+        (model.py:70-72, 132-136), nmse and psnr (model.py:20-30, psnr range 4) of the same decoder
+        output, from one more fused pass (metrics.slice_metrics) with the loss's ELU, slice mask and
+        cylinder.  The reference logs nmse / psnr while training too; here that would put a kernel into
+        the captured training step, so training logs the loss terms only."""
         x, num_valid_slices = batch
         loc, (commitment_loss, *_) = self(x)
         if x.dtype != torch.float32:
@@ -160,11 +165,14 @@ class VQVAE(nn.Module):
         loss, recon = Fn.recon_loss(loc, x, nvs, bool(self.pre_loss_f), *commitment_loss)
         log_dict = {'recon_loss_mean': recon}
         log_dict.update({f'commitment_loss_{i}': c for i, c in enumerate(commitment_loss)})
+        if quality:
+            q = slice_metrics(loc, x, nvs, activation="elu", cylinder=bool(self.pre_loss_f), psnr_range=4.0)
+            log_dict.update({'ssim_mean': q.ssim, 'nmse': q.nmse, 'psnr': q.psnr})
         self.log('recon loss', recon, prog_bar=True, logger=False)
         return loss, log_dict
 
-    def huber(self, batch, batch_idx, **pre_loss_f_metrics):
-        return self.loc_metric(batch, batch_idx)
+    def huber(self, batch, batch_idx, quality=False, **pre_loss_f_metrics):
+        return self.loc_metric(batch, batch_idx, quality=quality)
 
     def _parse_input_args(self, args: Namespace):
         """model.py:165-210"""

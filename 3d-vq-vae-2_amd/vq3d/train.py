@@ -19,7 +19,9 @@ ModelCheckpoint), restated here without that dependency:
   * CTDataModule(path, batch_size, num_workers=5, rescale_input) (train.py:52);
   * 'ddp': one process per GPU, DistributedSampler sharding, the bucketed RCCL gradient average
     of vq3d.parallel (overlapped with backward) and the Quantizers' fused EMA all-reduce;
-  * validation every val_check_interval of an epoch (val_recon_loss_mean, eval mode);
+  * validation every val_check_interval of an epoch (eval mode): val_recon_loss_mean and the
+    reference's quality metrics val_ssim_mean / val_nmse / val_psnr (vq3d.metrics), averaged over
+    the batches of every rank and printed;
   * ModelCheckpoint(save_top_k=1, save_last=True, monitor='val_recon_loss_mean') (train.py:56):
     last.ckpt after every validation, the best one as epoch=E-step=S.ckpt (PL 1.2 layout,
     vq3d.checkpoint);
@@ -150,21 +152,29 @@ def _to_device(batch, dev):
     return x.to(dev, non_blocking=True).float(), torch.as_tensor(nvs).to(dev)
 
 
+VAL_KEYS = ("val_recon_loss_mean", "val_ssim_mean", "val_nmse", "val_psnr")
+
+
 def validate(model, loader, dev):
+    """The mean of every VAL_KEYS value over the validation batches (all ranks): returns the
+    monitored one (val_recon_loss_mean, None without batches) and leaves them all in
+    model.val_metrics."""
     model.eval()
-    tot, n = 0.0, 0
+    tot, n = torch.zeros(len(VAL_KEYS), dtype=torch.float64, device=dev), 0
     with torch.no_grad():
         for batch in loader:
             x, nvs = _to_device(batch, dev)
             model.validation_step((x, nvs), n)
-            tot += float(model.logged["val_recon_loss_mean"])
+            tot += torch.stack([model.logged[k].double() for k in VAL_KEYS])
             n += 1
     model.train()
+    t = torch.cat([tot, torch.tensor([float(n)], dtype=torch.float64, device=dev)])
     if torch.distributed.is_initialized():
-        t = torch.tensor([tot, float(n)], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t)
-        tot, n = float(t[0]), int(t[1])
-    return tot / n if n else None
+    t = t.tolist()
+    n = int(t[-1])
+    model.val_metrics = {k: v / n for k, v in zip(VAL_KEYS, t)} if n else {}
+    return model.val_metrics.get(VAL_KEYS[0])
 
 
 def main(args: Namespace, datamodule=None):
@@ -249,6 +259,9 @@ def _fit(args, model, opt, reducer, ckpt, datamodule, rank, world, dev, epoch0, 
                     print(f"epoch {epoch} step {step} loss {history[-1][1]:.6f}", flush=True)
             if (i + 1) % val_every == 0 or (i + 1) == n_batches:
                 score = validate(model, vloader, dev) if len(val_ds) else None
+                if rank == 0 and score is not None:
+                    print(f"epoch {epoch} step {step} " + " ".join(f"{k} {v:.6f}" for k, v in model.val_metrics.items()),
+                          flush=True)
                 if rank == 0:  # PL's global_step is still this batch's 0-based index here
                     ckpt(model, opt, epoch, step - 1, score, args.max_steps, scaler)
             if args.max_steps is not None and step >= args.max_steps:

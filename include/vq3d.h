@@ -448,6 +448,29 @@ int vq3d_recon_loss_bwd(int32_t dtype, const void *dec, const float *x, const in
 /* number of (h, w) pixels inside the cylinder (host function) */
 int64_t vq3d_cylinder_count(int32_t h, int32_t w);
 
+/* --- validation metrics: slice-wise SSIM (SSIM3DSlices, metrics/evaluate.py:27-36, logged by
+ * validation_step, model.py:132-136), NMSE and PSNR (metrics/evaluate.py:18-24), one fused pass ---
+ * pred (dtype F32 / BF16 / F16) and target (fp32): contiguous (batch, 1, h, w, dd) volumes, dd innermost.
+ * p = act(pred) (activation 1: ELU, 0: identity), p = 0 where d >= nvs[b] (as the reconstruction
+ * loss masks padded slices); fp32 arithmetic from there on.  Every (b, d) is one 2-D slice over
+ * (h, w); its SSIM is the mean over the (h - 10)(w - 10) positions of an 11 x 11 Gaussian window
+ * (sigma 1.5, normalised) that lie wholly inside the slice, of
+ *   (2 mu_p mu_t + c1)(2 s_pt + c2) / ((mu_p^2 + mu_t^2 + c1)(s_pp + s_tt + c2)),
+ * c1 = (k1 R)^2, c2 = (k2 R)^2, with the windowed means mu and (co)variances s = E[ab] - mu_a mu_b.
+ * R = data_range when > 0, else max(max p - min p, max t - min t) over the whole batch (one more
+ * pass over both volumes; a computed R of 0 gives NaN).
+ * ssim_per_slice: [batch][dd] device floats.  stats: 5 device floats {ssim (the mean of the
+ * batch * dd slice values, padded slices included), mse = sum (p - t)^2 / count, nmse = sum (p - t)^2
+ * / sum t^2, psnr = 10 log10(psnr_range^2 / mse), the R used}; the three error figures run over
+ * every voxel, or with cylinder != 0 over the centre cylinder the loss sees.
+ * Deterministic (fixed-order partial sums through a workspace of vq3d_slice_metrics_workspace_size
+ * bytes, final sums in double), no atomics, no host synchronisation.  h, w >= 11. */
+size_t vq3d_slice_metrics_workspace_size(int32_t batch, int32_t h, int32_t w, int32_t dd);
+int vq3d_slice_metrics(int32_t dtype, const void *pred, const float *target, const int64_t *nvs, int32_t batch,
+                       int32_t h, int32_t w, int32_t dd, int32_t activation, int32_t cylinder, float data_range,
+                       float k1, float k2, float psnr_range, float *ssim_per_slice, float *stats, void *workspace,
+                       vq3d_stream_t stream);
+
 /* --- EvoNorm-S0 (evonorm.py:8-76), batch 1 --- */
 size_t vq3d_evonorm_workspace_size(int32_t channels, int64_t voxels);
 int vq3d_evonorm_fwd(int32_t dtype, const void *x, int32_t channels, int64_t voxels, const float *v,
