@@ -9,4 +9,14 @@ from .metrics import SSIM3DSlices, SliceMetrics, nmse, psnr, slice_metrics  # no
 
 __all__ = ["VQVAE", "default_args", "Encoder2", "Decoder", "PreActFixupResBlock", "FixupResBlock",
            "EvonormResBlock", "Quantizer", "ResizeConv3D", "EvoNorm3DS0", "DownBlock", "UpBlock",
-           "PreQuantizationConditioning", "Conv3d", "slice_metrics", "SliceMetrics", "SSIM3DSlices", "nmse", "psnr"]
+           "PreQuantizationConditioning", "Conv3d", "slice_metrics", "SliceMetrics", "SSIM3DSlices", "nmse", "psnr",
+           "sample_codes"]
+
+
+def __getattr__(name):
+    # vq3d.sample is also the `python -m vq3d.sample` program: importing it here, ahead of its run as
+    # __main__, would execute the module twice (runpy warns), so sample_codes resolves on first use
+    if name == "sample_codes":
+        from .sample import sample_codes
+        return sample_codes
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -143,6 +143,8 @@ _SIGS = {
     "vq3d_causal_attn_fwd_ex": (c_int, [c_int] * 6 + [c_float] + [P] * 7),
     "vq3d_causal_attn_bwd_ex": (c_int, [c_int] * 6 + [c_float] + [P] * 8 + [c_size] + [P] * 4),
     "vq3d_elu_bwd_from_output": (c_int, [c_int, P, P, P, c_i64, P]),
+    "vq3d_prior_sample_step": (c_int, [c_int, P, c_i64, c_int, P, P, c_int, P, c_float, P, c_i64, c_int, P, P, c_i64,
+                                       c_int, P, P]),
     "vq3d_last_error": (ctypes.c_char_p, []),
     "vq3d_version": (ctypes.c_char_p, []),
 }

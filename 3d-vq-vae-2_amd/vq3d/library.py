@@ -16,6 +16,8 @@ vqvae/layers.py:134-171 nn.Conv3d, :685-728 the Quantizer, model.py:115-163 the 
     vq3d::recon_loss / recon_loss_backward    smooth-L1 reconstruction + commitment sum (model.py:115-163)
     vq3d::slice_metrics                       validation SSIM / NMSE / PSNR (model.py:20-30, 132-136;
                                               no autograd: a metric, not a loss)
+    vq3d::prior_sample_step                   the prior sampler's head + draw at one raster position
+                                              (pixel_model/pixelsnail.py:256-269; in place, no autograd)
 
 Each operator runs exactly the kernels of the ctypes path (the same autograd.Function bodies of
 vq3d.functional, driven through a stand-in context), so `vq3d.functional.set_binding("library")`
@@ -546,6 +548,15 @@ def slice_metrics(pred: Tensor, target: Tensor, nvs: Tensor, elu: bool, cylinder
     return list(metrics.slice_metrics_kernel(pred, target, nvs, elu, cylinder, data_range, k1, k2, psnr_range))
 
 
+@torch.library.custom_op("vq3d::prior_sample_step", mutates_args=("onehot", "codes", "logits_out"))
+def prior_sample_step(hidden: Tensor, weight: Tensor, bias: Tensor, pos: Tensor, temperature: float, seed: Tensor,
+                      sample_base: int, onehot: Tensor, codes: Tensor, logits_out: Optional[Tensor]) -> None:
+    """row *pos of onehot and codes (and logits_out) from the prefix's hidden rows (vq3d.sample.sample_step
+    is the public form)"""
+    from . import sample
+    sample.sample_step_kernel(hidden, weight, bias, pos, temperature, seed, sample_base, onehot, codes, logits_out)
+
+
 def upsample(x):
     return _call("upsample2x", (x,), (x,))
 
@@ -665,6 +676,11 @@ def _slice_metrics_fake(pred, target, nvs, elu, cylinder, data_range, k1, k2, ps
             torch.empty(5, dtype=torch.float32, device=pred.device)]
 
 
+@torch.library.register_fake("vq3d::prior_sample_step")
+def _prior_sample_step_fake(hidden, weight, bias, pos, temperature, seed, sample_base, onehot, codes, logits_out):
+    return None
+
+
 for _n in ("conv3d_backward", "preact_block_backward", "preact_run_backward", "parse_input_backward",
            "recon_loss_backward"):
     torch.library.register_fake(f"vq3d::{_n}")(_eager_only(_n))
@@ -672,4 +688,4 @@ for _n in ("conv3d_backward", "preact_block_backward", "preact_run_backward", "p
 
 OPS = ("conv3d", "conv3d_backward", "preact_block", "preact_block_backward", "preact_run", "preact_run_backward",
        "vq_init", "vq_nearest", "vq_nearest_backward", "vq_ema", "parse_input", "parse_input_backward", "upsample2x",
-       "upsample2x_backward", "recon_loss", "recon_loss_backward", "slice_metrics")
+       "upsample2x_backward", "recon_loss", "recon_loss_backward", "slice_metrics", "prior_sample_step")

@@ -812,11 +812,17 @@ class CausalAttentionPixelBlock(nn.Module):
 
 
 # ============================================================================================ model
-def background_list(b, dims, dtype, device):
-    """_generate_background (pixelsnail.py:283-293) per stream: the (d, h, w) linspace grids."""
+def background_list(b, dims, dtype, device, full_dims=None):
+    """_generate_background (pixelsnail.py:283-293) per stream: the (d, h, w) linspace grids.  With
+    full_dims = (D, h, w), dims is the first dims[0] slabs of a D-slab grid and the result is that
+    crop of the full-size background (the sampler's `background[current_slice]`, pixelsnail.py:259),
+    not a fresh linspace over the crop."""
     d, h, w = dims
+    fd, fh, fw = dims if full_dims is None else full_dims
+    if (fh, fw) != (h, w) or d > fd:
+        raise ValueError(f"a {tuple(dims)} input is no slab prefix of a {tuple(full_dims)} grid")
     g = torch.cat([
-        torch.linspace(-1, 1, d, device=device).view(1, 1, -1, 1, 1).expand(b, 1, d, h, w),
+        torch.linspace(-1, 1, fd, device=device)[:d].view(1, 1, -1, 1, 1).expand(b, 1, d, h, w),
         torch.linspace(-1, 1, h, device=device).view(1, 1, 1, -1, 1).expand(b, 1, d, h, w),
         torch.linspace(-1, 1, w, device=device).view(1, 1, 1, 1, -1).expand(b, 1, d, h, w),
     ], dim=1).to(dtype)
@@ -833,6 +839,7 @@ class PixelSNAIL(nn.Module):
 
     def __init__(self, args, compute_dtype="bf16"):
         super().__init__()
+        self.hparams = {"args": args}  # what checkpoint.save_checkpoint stores (PL's save_hyperparameters)
         self._parse_input_args(args)
         self.compute_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(compute_dtype, torch.float32)
         self.parse_input = nn.Conv3d(in_channels=self.input_dim, out_channels=self.model_dim, kernel_size=1)
@@ -893,6 +900,13 @@ class PixelSNAIL(nn.Module):
 
     def logits(self, onehot):
         """forward (pixelsnail.py:301-320) of a one-hot (b, K, d, h, w) input; fp32 logits."""
+        return pointwise(self.hidden(onehot), self.parse_output.weight, self.parse_output.bias).float()
+
+    def hidden(self, onehot, full_dims=None):
+        """the forward up to parse_output: the (b, model_dim, d, h, w) channels-last input of the output
+        head, in the compute dtype.  full_dims = (D, h, w): onehot holds the first onehot.shape[2]
+        slabs of a D-slab grid (the sampler's causally complete prefix) and the background channels
+        are the matching crop of the full-size background."""
         b = onehot.shape[0]
         dims = tuple(onehot.shape[2:])
         _compute[0] = self.compute_dtype
@@ -906,7 +920,7 @@ class PixelSNAIL(nn.Module):
                 fl.refresh_shadow(self.compute_dtype)
                 _shadow[0] = (fl, self.compute_dtype)
         x = cl(pointwise(x, self.parse_input.weight, self.parse_input.bias))
-        bg = background_list(b, dims, self.compute_dtype, x.device)
+        bg = background_list(b, dims, self.compute_dtype, x.device, full_dims)
         if self.compute_dtype != torch.float32:
             # 16-bit: the background channels padded with zeros to a multiple of 8, so the attention
             # projections' inputs (2 C + 3 / C + 3 channels) are 16-byte voxel rows for vq3d_rows_gemm
@@ -932,8 +946,7 @@ class PixelSNAIL(nn.Module):
         finally:
             _LANES[0] = None
             _LSTATE[0] = None
-        s = _operand(stack[0] + stack[1] + stack[2])
-        return pointwise(s, self.parse_output.weight, self.parse_output.bias).float()
+        return _operand(stack[0] + stack[1] + stack[2])
 
     def forward(self, data, background=None, attn_mask=None, condition=None, condition_cache=None):
         if condition is not None or condition_cache is not None:

@@ -587,6 +587,35 @@ int vq3d_causal_attn_bwd_ex(int32_t dtype, int32_t nprob, int32_t n, int32_t nh,
                             const void *out, const void *gout, const float *lse, void *workspace,
                             size_t workspace_bytes, void *gq, void *gk, void *gv, vq3d_stream_t stream);
 
+/* --- prior sampling: the output head and the draw of one raster position (PixelSNAIL.sample,
+ * pixel_model/pixelsnail.py:219-272: parse_output at the position, then the hard Gumbel-softmax) ---
+ * One launch, one workgroup per sample b of the batch, with p = *pos:
+ *   logit[k] = bias[k] + sum_c hidden[b][p][c] * W[k][c]     fp32 accumulation; when hidden is 16-bit
+ *              W is rounded to that format on load (as the 16-bit forward's GEMM operand is);
+ *              nothing is rounded after the sum
+ *   code     = argmax_k (logit[k] / temperature + g_k), the first index on a tie;
+ *              temperature == 0: argmax_k logit[k], no noise
+ *   g_k      = -logf(-logf(u_k)) in fp32 (accurate logf), u_k = (float(hash >> 9) + 0.5f) * 2^-23:
+ *              exactly representable, never 0 or 1
+ *   hash     = mix(mix(mix(lo ^ hi * 0x9E3779B1 ^ s_lo * 0xC2B2AE3D ^ s_hi * 0x165667B1)
+ *                      ^ p_lo * 0x85EBCA77 ^ p_hi * 0x9E3779B1) ^ k * 0x27D4EB2F)
+ *              in 32-bit arithmetic, with lo / hi the halves of *seed, s_lo / s_hi those of the global
+ *              sample index s = sample_base + b, p_lo / p_hi those of p, and the lowbias32 finisher
+ *              mix: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ * Then codes[b][p] = code, the row onehot[b][p][:] becomes the one-hot of code, and (logits_out
+ * != NULL) logits_out[b][:] = logit.  The draw is code ~ softmax(logit / temperature); temperature 1 is
+ * the reference's distribution at any tau (its hard sample is argmax(logit + g) whatever tau is).
+ * hidden: [batch][hidden_positions][c] channels-last rows, hidden_dtype F32 / BF16 / F16.  weight
+ * [k][c] and bias [k]: fp32.  onehot: [batch][npos][k], onehot_dtype F32 / BF16 / F16.  codes: int64
+ * [batch][npos].  logits_out: fp32 [batch][k] or NULL.  pos (int64) and seed are device scalars,
+ * read and never written: a captured graph replays while the caller advances them.
+ * *pos outside [0, min(npos, hidden_positions)): nothing is written.  8 <= k <= 1024; c a multiple
+ * of 8, <= 1024.  Deterministic: no atomics, no host synchronisation. */
+int vq3d_prior_sample_step(int32_t hidden_dtype, const void *hidden, int64_t hidden_positions, int32_t c,
+                           const float *weight, const float *bias, int32_t k, const int64_t *pos, float temperature,
+                           const uint64_t *seed, int64_t sample_base, int32_t onehot_dtype, void *onehot,
+                           int64_t *codes, int64_t npos, int32_t batch, float *logits_out, vq3d_stream_t stream);
+
 const char *vq3d_last_error(void);
 const char *vq3d_version(void);
 
