@@ -145,6 +145,8 @@ _SIGS = {
     "vq3d_elu_bwd_from_output": (c_int, [c_int, P, P, P, c_i64, P]),
     "vq3d_prior_sample_step": (c_int, [c_int, P, c_i64, c_int, P, P, c_int, P, c_float, P, c_i64, c_int, P, P, c_i64,
                                        c_int, P, P]),
+    "vq3d_prior_head_loss_fwd": (c_int, [c_int, c_i64, c_int, c_int, P, c_i64, P, c_i64] + [P] * 7 + [P]),
+    "vq3d_prior_head_loss_bwd": (c_int, [c_int, c_i64, c_int, c_int, P, c_i64, P, c_i64] + [P] * 7 + [c_i64, P]),
     "vq3d_last_error": (ctypes.c_char_p, []),
     "vq3d_version": (ctypes.c_char_p, []),
 }

@@ -18,6 +18,8 @@ vqvae/layers.py:134-171 nn.Conv3d, :685-728 the Quantizer, model.py:115-163 the 
                                               no autograd: a metric, not a loss)
     vq3d::prior_sample_step                   the prior sampler's head + draw at one raster position
                                               (pixel_model/pixelsnail.py:256-269; in place, no autograd)
+    vq3d::prior_head_loss / _backward         the prior's output head fused with the cross-entropy and
+                                              the argmax (pixel_model/pixelsnail.py:78-82, 112-161)
 
 Each operator runs exactly the kernels of the ctypes path (the same autograd.Function bodies of
 vq3d.functional, driven through a stand-in context), so `vq3d.functional.set_binding("library")`
@@ -557,6 +559,53 @@ def prior_sample_step(hidden: Tensor, weight: Tensor, bias: Tensor, pos: Tensor,
     sample.sample_step_kernel(hidden, weight, bias, pos, temperature, seed, sample_base, onehot, codes, logits_out)
 
 
+@torch.library.custom_op("vq3d::prior_head_loss", mutates_args=())
+def prior_head_loss(hidden: Tensor, weight: Tensor, bias: Tensor, target_a: Tensor, target_b: Optional[Tensor],
+                    lam: Optional[Tensor]) -> List[Tensor]:
+    """[loss (n,) fp32, pred (n,) int32, lse (n,) fp32] of 16-bit rows (n, c) with the (K, c) weight in the rows'
+    format: the prior's fused output head + cross-entropy + argmax (vq3d.head_loss.head_loss is the public
+    form)"""
+    from . import head_loss as H
+    return list(H.head_loss_fwd_kernel(hidden, weight, bias, target_a, target_b, lam))
+
+
+@torch.library.custom_op("vq3d::prior_head_loss_backward", mutates_args=())
+def prior_head_loss_backward(gloss: Tensor, hidden: Tensor, weight: Tensor, bias: Tensor, target_a: Tensor,
+                             target_b: Optional[Tensor], lam: Optional[Tensor], lse: Tensor) -> Tensor:
+    """dlogits (n, K) in the rows' format, the logits recomputed"""
+    from . import head_loss as H
+    return H.head_loss_bwd_kernel(gloss, hidden, weight, bias, target_a, target_b, lam, lse)
+
+
+def _hl_setup(ctx, inputs, output):
+    ctx.save_for_backward(*[t for t in inputs if t is not None], output[2])
+    ctx.has = [t is not None for t in inputs]
+    ctx.mark_non_differentiable(output[1], output[2])
+    ctx.set_materialize_grads(False)
+
+
+def _hl_bwd(ctx, grads):
+    """a direct torch.ops.vq3d.prior_head_loss call under autograd: the gradients of hidden, of the 16-bit
+    weight and of the bias come back through autograd (the model's path, vq3d.head_loss.HeadLossFn, adds
+    the parameters' into their gradient buffers instead)"""
+    from . import head_loss as H
+    saved = list(ctx.saved_tensors)
+    lse = saved.pop()
+    it = iter(saved)
+    hidden, weight, bias, ta, tb, lam = (next(it) if h else None for h in ctx.has)
+    if grads[0] is None:
+        return None, None, None, None, None, None
+    dlogits = torch.ops.vq3d.prior_head_loss_backward(grads[0].float().contiguous(), hidden, weight, bias, ta, tb, lam,
+                                                      lse)
+    dw = ops.zero_(torch.empty(weight.shape, dtype=torch.float32, device=weight.device))
+    db = ops.zero_(torch.empty(bias.shape, dtype=torch.float32, device=bias.device))
+    gx = H.head_grads(dlogits, hidden, weight, dw, db, ctx.needs_input_grad[0])
+    return gx, dw.to(weight.dtype), db, None, None, None
+
+
+_register("prior_head_loss", _hl_bwd, _hl_setup, (0, 1, 2))
+
+
 def upsample(x):
     return _call("upsample2x", (x,), (x,))
 
@@ -681,6 +730,18 @@ def _prior_sample_step_fake(hidden, weight, bias, pos, temperature, seed, sample
     return None
 
 
+@torch.library.register_fake("vq3d::prior_head_loss")
+def _prior_head_loss_fake(hidden, weight, bias, target_a, target_b, lam):
+    n = hidden.shape[0]
+    f = torch.empty(n, dtype=torch.float32, device=hidden.device)
+    return [f, torch.empty(n, dtype=torch.int32, device=hidden.device), torch.empty_like(f)]
+
+
+@torch.library.register_fake("vq3d::prior_head_loss_backward")
+def _prior_head_loss_backward_fake(gloss, hidden, weight, bias, target_a, target_b, lam, lse):
+    return torch.empty((hidden.shape[0], weight.shape[0]), dtype=hidden.dtype, device=hidden.device)
+
+
 for _n in ("conv3d_backward", "preact_block_backward", "preact_run_backward", "parse_input_backward",
            "recon_loss_backward"):
     torch.library.register_fake(f"vq3d::{_n}")(_eager_only(_n))
@@ -688,4 +749,5 @@ for _n in ("conv3d_backward", "preact_block_backward", "preact_run_backward", "p
 
 OPS = ("conv3d", "conv3d_backward", "preact_block", "preact_block_backward", "preact_run", "preact_run_backward",
        "vq_init", "vq_nearest", "vq_nearest_backward", "vq_ema", "parse_input", "parse_input_backward", "upsample2x",
-       "upsample2x_backward", "recon_loss", "recon_loss_backward", "slice_metrics", "prior_sample_step")
+       "upsample2x_backward", "recon_loss", "recon_loss_backward", "slice_metrics", "prior_sample_step",
+       "prior_head_loss", "prior_head_loss_backward")

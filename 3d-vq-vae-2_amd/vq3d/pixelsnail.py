@@ -984,6 +984,27 @@ class PixelSNAIL(nn.Module):
         loss = unreduced.mean()
         return loss, {"bits_per_dim": loss.detach() / np.log(2)}
 
+    def loss_rows(self, onehot, codes, mix=None):
+        """The per-position loss and prediction of a prepared one-hot (b, K, d, h, w) input: `hidden`
+        followed by the fused output head (vq3d.head_loss: no logits tensor, the loss from the
+        unrounded fp32 logits).  Returns (loss (b, d, h, w) fp32, pred (b, d, h, w) int64);
+        loss.mean() is cross_entropy_onehot's loss.  mix = (lam_t, index_t), DEVICE tensors -- fp32
+        0-d lam_t, int64 (b,) index_t: the input is lam x + (1 - lam) x[index] and the loss
+        lam CE(y) + (1 - lam) CE(y[index]) (train_helpers.py:20-63), blend and weights read from the
+        tensors when the kernels run, so a captured step replays with new draws copied into them."""
+        from .head_loss import head_loss
+        tb = lam_t = None
+        x = onehot
+        if mix is not None:
+            lam_t, index_t = mix
+            x = onehot.float()
+            x = lam_t * x + (1 - lam_t) * x[index_t]
+            tb = codes[index_t].reshape(-1)
+        hid = self.hidden(x)
+        rows = hid.permute(0, 2, 3, 4, 1).reshape(-1, hid.shape[1])
+        loss, pred = head_loss(rows, self.parse_output.weight, self.parse_output.bias, codes.reshape(-1), tb, lam_t)
+        return loss.view(codes.shape), pred.view(codes.shape)
+
     def training_step(self, batch, batch_idx):
         return self.cross_entropy(batch, batch_idx, mode="train")[0]
 

@@ -273,9 +273,10 @@ def _fit(args, model, opt, reducer, ckpt, datamodule, rank, world, dev, epoch0, 
     return model, opt, history, ckpt
 
 
-def launch_ranks(args, argv):
+def launch_ranks(args, argv, module="vq3d.train"):
     """The 'ddp' self-launch (train.py:25-27): the exit code of the N ranks this command started
-    when --gpus asks for more than one GPU and this process is not already a rank, else None."""
+    (each running `module`) when --gpus asks for more than one GPU and this process is not already a
+    rank, else None."""
     from . import launch
     if launch.is_rank_process() or args.accelerator not in (None, "ddp"):
         return None
@@ -285,7 +286,7 @@ def launch_ranks(args, argv):
     env = dict(os.environ)
     pkg = str(Path(__file__).resolve().parent.parent)  # the ranks import vq3d from the same tree
     env["PYTHONPATH"] = pkg + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
-    return launch.run_ranks(n, "vq3d.train", list(argv), module=True, env=env)
+    return launch.run_ranks(n, module, list(argv), module=True, env=env)
 
 
 def cli(argv=None):

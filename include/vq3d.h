@@ -616,6 +616,35 @@ int vq3d_prior_sample_step(int32_t hidden_dtype, const void *hidden, int64_t hid
                            const uint64_t *seed, int64_t sample_base, int32_t onehot_dtype, void *onehot,
                            int64_t *codes, int64_t npos, int32_t batch, float *logits_out, vq3d_stream_t stream);
 
+/* --- prior training: the output head fused with its loss (parse_output, pixel_model/pixelsnail.py:78-82,
+ * and the cross-entropy of shared_step, :112-161, with mixup's two targets, train_helpers.py:50-63),
+ * without the [nrows][k] logits in memory.  Per voxel row v:
+ *   logit[j] = bias[j] + sum_c hidden[v][c] * weight[j][c]   fp32 accumulation on the matrix cores; nothing is
+ *              rounded after the sum (the logits vq3d_prior_sample_step draws from)
+ *   lse[v]   = log sum_j exp(logit[j])                       max-subtracted online softmax, fp32
+ *   loss[v]  = lse[v] - lam * logit[target_a[v]] - (1 - lam) * logit[target_b[v]]
+ *   pred[v]  = the first index of the largest logit (int32)
+ * hidden: [nrows][c] 16-bit rows at stride ldh; weight: [k][c] rows of the same format at stride ldw; bias
+ * fp32 [k]; target_a int64 [nrows]; target_b int64 [nrows] or NULL; lam a device scalar that is read and
+ * never written (a captured graph replays with a new value in it); lam NULL or target_b NULL: lam = 1.
+ * Targets are compared against j and never used as addresses: one outside [0, k) matches no code and
+ * contributes 0.  loss, lse: fp32 [nrows].
+ * The backward recomputes the logits (the same device code: bit-identical) and writes
+ *   dlogits[v][j] = round16(gloss[v] * (exp(logit[j] - lse[v]) - lam [j = target_a[v]] - (1 - lam) [j = target_b[v]]))
+ * as 16-bit rows at stride ldg, gloss fp32 [nrows] the gradient of the loss vector; dHidden, dW and dbias
+ * then are vq3d_rows_gemm (trans_w = 1) and vq3d_rows_wgrad of dlogits.
+ * dtype VQ3D_BF16 | VQ3D_F16 only; 8 <= k <= 1024, k % 8 == 0; c % 8 == 0, c <= 1024; strides multiples of 8;
+ * hidden, weight, dlogits 16-byte aligned.  Deterministic: fixed-order reductions, no atomics, no workspace,
+ * no host synchronisation. */
+int vq3d_prior_head_loss_fwd(int32_t dtype, int64_t nrows, int32_t c, int32_t k, const void *hidden, int64_t ldh,
+                             const void *weight, int64_t ldw, const float *bias, const int64_t *target_a,
+                             const int64_t *target_b, const float *lam, float *loss, float *lse, int32_t *pred,
+                             vq3d_stream_t stream);
+int vq3d_prior_head_loss_bwd(int32_t dtype, int64_t nrows, int32_t c, int32_t k, const void *hidden, int64_t ldh,
+                             const void *weight, int64_t ldw, const float *bias, const int64_t *target_a,
+                             const int64_t *target_b, const float *lam, const float *lse, const float *gloss,
+                             void *dlogits, int64_t ldg, vq3d_stream_t stream);
+
 const char *vq3d_last_error(void);
 const char *vq3d_version(void);
 
