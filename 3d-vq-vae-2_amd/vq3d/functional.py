@@ -15,8 +15,6 @@ from .ops import ConvGeom
 from . import flat as _flat
 from .parallel import grads_ready, sum_allreduce
 
-CL = torch.channels_last_3d
-
 
 _BINDING = ["ctypes"]
 
@@ -50,11 +48,11 @@ def preact_block(x, blk):
     return PreActBlockFn.apply(x, blk, *param_edges(blk._fn_params, x))
 
 
-def preact_run(fn, x, plan):
+def preact_run(kind, x, plan):
     lb = _library()
     if lb is not None:
-        return lb.run(fn, x, plan)
-    return fn.apply(x, plan, *param_edges(plan.params, x))
+        return lb.run(kind, x, plan)
+    return RUN_FNS[kind].apply(x, plan, *param_edges(plan.params, x))
 
 
 def upsample(x):
@@ -97,19 +95,7 @@ def param_edges(params, *acts):
     return params
 
 
-def grad_buf(p):
-    """fp32 gradient buffer of parameter p (allocated zeroed if the caller set it to None)."""
-    if p is None:
-        return None
-    if p.grad is None:
-        p.grad = ops.zero_(torch.empty_like(p))
-    return p.grad
-
-
-def _cl(g):
-    if g.is_contiguous(memory_format=CL) or (g.shape[1] == 1 and g.is_contiguous()):
-        return g
-    return g.contiguous(memory_format=CL)
+grad_buf, block_grads, _cl = ops.grad_buf, ops.block_grads, ops.to_cl
 
 
 def mode_geometry(mode):
@@ -119,6 +105,75 @@ def mode_geometry(mode):
     if mode in ("same", "out"):
         return 3, 1, 1, False
     return 3, 1, 1, True
+
+
+# ============================================================================================ routes
+# Which fused engine a block / a run of blocks reaches is decided HERE, as pure functions of
+# (dtype, shape, block) over the library's host-only *_supported / *_plan queries, so they run
+# without a GPU (tests/test_block_routes_cpu.py pins the table, as test_conv_routes_cpu.py pins
+# csrc/conv3d.hip's route()).
+def _plain(blk):
+    """no skip conv, a stride-1 3x3x3 branch conv on the input grid: what every fused engine takes"""
+    k, s, _, up = mode_geometry(blk.mode)
+    return blk.skip_conv is None and k == 3 and s == 1 and not up
+
+
+def block_path(dtype, shape, blk):
+    """The path of ONE block (PreActBlockFn): "tiny" | "small" | "mid" (fused block kernels) | "convs"."""
+    nb = blk.branch_conv1.weight.shape[0]
+    if not _plain(blk):
+        return "convs"
+    if ops.tiny_blocks_enabled() and ops.preact_tiny_supported(shape, nb):
+        return "tiny"
+    if ops.small_supported(dtype, shape, nb):
+        return "small"
+    return "mid" if ops.mid_supported(dtype, shape, nb) else "convs"
+
+
+def stack_eligible(blk):
+    return type(blk).__name__ == "PreActFixupResBlock" and _plain(blk)
+
+
+def run_route(dtype, shape, blk, nrun, small_only=False):
+    """The engine of a maximal run of `nrun` stack-eligible blocks with blk's (in_channels, branch)
+    (layers.BlockStack): "stack" | "wide" | "mid" | "small" (a key of RUN_FNS), or None: block by
+    block.  small_only: the Down / UpBlock stacks, which fuse few-channel runs only."""
+    if not _run_block(shape, blk):
+        return None
+    nb = blk.branch_conv1.weight.shape[0]
+    if not small_only:
+        if nrun >= 2 and ops.stack_supported(dtype, shape, nb):
+            return "stack"
+        if ops.wide_supported(dtype, shape, nb):  # a single block too
+            return "wide"
+        if nrun >= 2 and ops.mid_supported(dtype, shape, nb):
+            return "mid"
+    return "small" if nrun >= 2 and _small_run(dtype, shape, nb) else None
+
+
+def _run_block(shape, blk):
+    return stack_eligible(blk) and len(shape) == 5 and shape[1] == blk.in_channels
+
+
+def _small_run(dtype, shape, nb):
+    return ops.small_supported(dtype, shape, nb) and ops.small_bwd_fused(shape)
+
+
+def _eligible(x, blk, supported):
+    """one run engine's own condition on a tensor (False off the GPU), whatever run_route's order gives"""
+    return x.is_cuda and _run_block(x.shape, blk) and supported(x.dtype, x.shape, blk.branch_conv1.weight.shape[0])
+
+
+def wide_eligible(x, blk):
+    return _eligible(x, blk, ops.wide_supported)
+
+
+def mid_run_eligible(x, blk):
+    return _eligible(x, blk, ops.mid_supported)
+
+
+def small_run_eligible(x, blk):
+    return _eligible(x, blk, _small_run)
 
 
 # ============================================================================================ PreAct block
@@ -140,34 +195,23 @@ class PreActBlockFn(torch.autograd.Function):
         k, s, p, up = mode_geometry(blk.mode)
         g1 = ConvGeom(1)
         x = ops.as_cl(x)
-        ctx.tiny = (blk.skip_conv is None and not up and k == 3 and s == 1 and ops.tiny_blocks_enabled()
-                    and ops.preact_tiny_supported(x.shape, blk.branch_conv1.weight.shape[0]))
-        if ctx.tiny:
+        ctx.blk = blk
+        ctx.path = path = block_path(x.dtype, x.shape, blk)
+        if path == "tiny":
             # whole block in one launch (tiny_block.hip); t2 / t3 saved in fp32
             out, saved = ops.preact_tiny_fwd(x, blk)
-            ctx.blk = blk
             ctx.save_for_backward(x, saved)
             return out
-        ctx.small = False
         # no backward follows (eval / no_grad: the encode-only extraction path): the fused
         # kernels skip writing the saved intermediates
         save = any(ctx.needs_input_grad)
-        if (blk.skip_conv is None and not up and k == 3 and s == 1
-                and ops.preact_small_supported(x, blk.branch_conv1.weight.shape[0])):
-            # few-channel blocks: fused forward (preact_small.hip / preact_col.hip); t2 / t3 saved
-            # in bf16 as the unfused convs write them, so either backward applies
-            out, t2, t3 = ops.preact_small_fwd(x, blk, save=save)
-            ctx.blk = blk
-            ctx.small = ops.small_backward_fused(x)
-            ctx.save_for_backward(x, t2, t3, None)
-            return out
-        if (blk.skip_conv is None and not up and k == 3 and s == 1
-                and ops.preact_mid_supported(x, blk.branch_conv1.weight.shape[0])):
-            # 18-channel level: fused forward (2 launches) and backward (3 launches),
-            # preact_mid.hip
-            out, t2, t3 = ops.preact_mid_fwd(x, blk, save=save)
-            ctx.blk = blk
-            ctx.mid = True
+        if path in ("small", "mid"):
+            # few-channel blocks: fused forward (preact_small.hip / preact_col.hip); t2 / t3 saved in
+            # bf16 as the unfused convs write them, so either backward applies (fused_bwd: which).
+            # 18-channel level: fused forward (2 launches) and backward (3 launches), preact_mid.hip
+            out, t2, t3 = (ops.preact_small_fwd if path == "small" else ops.preact_mid_fwd)(x, blk, save=save)
+            if path == "small":
+                ctx.fused_bwd = ops.small_backward_fused(x)
             ctx.save_for_backward(x, t2, t3, None)
             return out
         t2 = ops.conv_fwd(x, blk.branch_conv1.weight, g1, pro=(blk.bias1a, blk.bias1b), act=(blk.bias2a, blk.bias2b))
@@ -186,30 +230,22 @@ class PreActBlockFn(torch.autograd.Function):
             res = x
         out = ops.conv_fwd(t3, blk.branch_conv3.weight, g1, scale=blk.scale, bias=blk.bias4, residual=res,
                            residual_up2=up)
-        ctx.blk = blk
         ctx.save_for_backward(x, t2, t3, tup)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        blk = ctx.blk
+        blk, path = ctx.blk, ctx.path
         g = _cl(g)
-        if ctx.tiny:
+        if path == "tiny":
             x, saved = ctx.saved_tensors
-            gb = grad_buf
-            names = {"dw1": blk.branch_conv1.weight, "dw2": blk.branch_conv2.weight, "dw3": blk.branch_conv3.weight,
-                     "dbias1a": blk.bias1a, "dbias1b": blk.bias1b, "dbias2a": blk.bias2a, "dbias2b": blk.bias2b,
-                     "dbias3a": blk.bias3a, "dbias3b": blk.bias3b, "dscale": blk.scale, "dbias4": blk.bias4}
-            g_x = ops.preact_tiny_bwd(g, x, saved, blk, {n: gb(t) for n, t in names.items()})
+            g_x = ops.preact_tiny_bwd(g, x, saved, blk, block_grads(blk))
             grads_ready(blk._fn_params)
             return (g_x, None) + (None,) * ctx.n_params
         x, t2, t3, tup = ctx.saved_tensors
-        if ctx.small or getattr(ctx, "mid", False):
-            names = {"dw1": blk.branch_conv1.weight, "dw2": blk.branch_conv2.weight, "dw3": blk.branch_conv3.weight,
-                     "dbias1a": blk.bias1a, "dbias1b": blk.bias1b, "dbias2a": blk.bias2a, "dbias2b": blk.bias2b,
-                     "dbias3a": blk.bias3a, "dbias3b": blk.bias3b, "dscale": blk.scale, "dbias4": blk.bias4}
-            bwd = ops.preact_small_bwd if ctx.small else ops.preact_mid_bwd
-            g_x = bwd(g, x, t2, t3, blk, {n: grad_buf(t) for n, t in names.items()})
+        if path == "mid" or (path == "small" and ctx.fused_bwd):
+            bwd = ops.preact_small_bwd if path == "small" else ops.preact_mid_bwd
+            g_x = bwd(g, x, t2, t3, blk, block_grads(blk))
             grads_ready(blk._fn_params)
             return (g_x, None) + (None,) * ctx.n_params
         k, s, p, up = mode_geometry(blk.mode)
@@ -246,27 +282,19 @@ class PreActBlockFn(torch.autograd.Function):
 
 
 # ============================================================================================ block stack
-_PRM = ("branch_conv1", "branch_conv2", "branch_conv3", "bias1a", "bias1b", "bias2a", "bias2b", "bias3a", "bias3b",
-        "scale", "bias4")
-
-
-def _prm_tensor(blk, n):
-    return getattr(blk, n).weight if n.startswith("branch_conv") else getattr(blk, n)
-
-
 class StackPlan:
     """Device tables of the parameter / gradient pointers of a run of blocks ([block][11], the
-    order of vq3d_preact_stack_fwd), rebuilt when the parameters move (flat.py re-views)."""
+    order of vq3d_preact_stack_fwd: ops.PRM), rebuilt when the parameters move (flat.py re-views)."""
 
     def __init__(self, blocks, out_dtype=None):
         self.blocks = list(blocks)
-        self.params = [_prm_tensor(b, n) for b in self.blocks for n in _PRM]
+        self.params = [p for b in self.blocks for p in ops.block_params(b)]
         self.key = None
         self.out_dtype = out_dtype  # a run Function's output storage (None: its input's)
 
     def grad_ptrs(self, i):
         """gradient buffer addresses of block i (in the table order), after tables()"""
-        return self.gptrs[i * len(_PRM): (i + 1) * len(_PRM)]
+        return self.gptrs[i * len(ops.PRM): (i + 1) * len(ops.PRM)]
 
     def tables(self, dev):
         # fast path: no view was re-attached since the last build (flat.VERSION) and every .grad is set
@@ -287,190 +315,50 @@ class StackPlan:
         return self.ptab, self.gtab
 
 
-class PreActStackFn(torch.autograd.Function):
-    """A run of identical PreActFixupResBlocks ('same', no skip) on a tiny grid: forward and
-    backward in one launch each (preact_stack.hip), the residual stream fp32 inside the run."""
+class _RunFn(torch.autograd.Function):
+    """A fused run of identical PreActFixupResBlocks ('same', no skip) as ONE autograd node.  Each
+    engine is a (run_fwd, run_bwd) pair of ops: run_fwd(x, plan, save) -> out, saved tensors;
+    run_bwd(g, plan, saved, in_dtype) -> gx, the parameter gradients accumulated into plan.params'
+    .grad.  save=False (eval / no_grad): the engines skip writing the saved intermediates."""
+    run_fwd = run_bwd = None
 
-    @staticmethod
-    def forward(ctx, x, plan, *params):
+    @classmethod
+    def forward(cls, ctx, x, plan, *params):
         ctx.n_params = len(params)
-        x = ops.as_cl(x)
-        b, c, h, w, d = x.shape
-        nb = plan.blocks[0].branch_conv1.weight.shape[0]
-        nblk = len(plan.blocks)
-        ptab, _ = plan.tables(x.device)
-        saved = torch.empty(L.query("vq3d_preact_stack_saved_floats", nblk, b, c, nb, h, w, d), dtype=torch.float32,
-                            device=x.device)
-        out = torch.empty_like(x, memory_format=ops.CL)
-        ops._timed("k_stackm_fwd", lambda: L.call("vq3d_preact_stack_fwd", L.dtype_code(x), nblk, b, c, nb, h, w, d,
-                                                  L.ptr(x), L.ptr(ptab), L.ptr(out), L.ptr(saved), L.stream()))
-        ctx.plan = plan
-        ctx.save_for_backward(saved)
-        ctx.shape = (b, c, nb, h, w, d)
+        out, saved = cls.run_fwd(x, plan, any(ctx.needs_input_grad))
+        ctx.plan, ctx.in_dtype = plan, x.dtype
+        ctx.save_for_backward(*saved)
         return out
 
-    @staticmethod
-    def backward(ctx, g):
-        (saved,) = ctx.saved_tensors
-        plan = ctx.plan
-        b, c, nb, h, w, d = ctx.shape
-        g = _cl(g)
-        ptab, gtab = plan.tables(g.device)
-        gx = torch.empty_like(g, memory_format=ops.CL)
-        nblk = len(plan.blocks)
-        nws = L.query("vq3d_preact_stack_bwd_workspace_bytes", nblk, b, c, nb, h, w, d)
-        ws = ops.workspace(nws, g.device)
-        ops._timed("k_stackm_bwd", lambda: L.call("vq3d_preact_stack_bwd_ws", L.dtype_code(g), nblk, b, c, nb, h, w, d,
-                                                  L.ptr(g), L.ptr(ptab), L.ptr(gtab), L.ptr(saved), L.ptr(gx),
-                                                  L.ptr(ws), max(nws, 256), L.stream()))
-        grads_ready(plan.params)
+    @classmethod
+    def backward(cls, ctx, g):
+        gx = cls.run_bwd(g, ctx.plan, ctx.saved_tensors, ctx.in_dtype)
+        grads_ready(ctx.plan.params)
         return (gx, None) + (None,) * ctx.n_params
 
 
-class PreActWideFn(torch.autograd.Function):
-    """A run of 72-channel / branch-36 PreActFixupResBlocks (preact_wide.hip): the weights of the
-    whole run packed once (one launch), then one fused launch per block forward and two per block
-    backward (data path, weight-gradient partials into a slice of one run workspace) plus one
-    fixed-order reduction launch for the whole run;
-    the residual and gradient streams fp32 inside the run."""
-
-    @staticmethod
-    def forward(ctx, x, plan, *params):
-        ctx.n_params = len(params)
-        x = ops.as_cl(x)
-        b, c, h, w, d = x.shape
-        nb = plan.blocks[0].branch_conv1.weight.shape[0]
-        ptab, _ = plan.tables(x.device)
-        img, per = ops.preact_wide_pack(ptab, len(plan.blocks), c, nb, x.device, dtype=x.dtype)
-        base = img.data_ptr()
-        xs = ops.cast(x, torch.float32)
-        save = any(ctx.needs_input_grad)
-        saved = []
-        for i, blk in enumerate(plan.blocks):
-            out, t2, t3 = ops.preact_wide_fwd(xs, base + i * per, blk, save=save, dtype=x.dtype)
-            if save:
-                saved += [xs, t2, t3]
-            xs = out
-        ctx.plan, ctx.per, ctx.in_dtype = plan, per, x.dtype
-        ctx.save_for_backward(img, *saved)
-        return ops.cast(xs, x.dtype)
-
-    @staticmethod
-    def backward(ctx, g):
-        img, *saved = ctx.saved_tensors
-        plan = ctx.plan
-        base = img.data_ptr()
-        gs = ops.cast(_cl(g), torch.float32)
-        run_ws, wbase, stride = ops.preact_wide_run_workspace(plan, gs.shape, gs.device)
-        batched = ops.batched_wgrad() and not ops.concurrent_wgrad()
-        run = [None] * len(plan.blocks)  # batched: (g, x, t2, t3) per block for one weight launch
-        for i in reversed(range(len(plan.blocks))):
-            blk = plan.blocks[i]
-            xs, t2, t3 = saved[3 * i: 3 * i + 3]
-            names = {"dw1": blk.branch_conv1.weight, "dw2": blk.branch_conv2.weight, "dw3": blk.branch_conv3.weight,
-                     "dbias1a": blk.bias1a, "dbias1b": blk.bias1b, "dbias2a": blk.bias2a, "dbias2b": blk.bias2b,
-                     "dbias3a": blk.bias3a, "dbias3b": blk.bias3b, "dscale": blk.scale, "dbias4": blk.bias4}
-            if batched:
-                run[i] = (gs, xs, t2, t3)
-            gs = ops.preact_wide_bwd(gs, xs, t2, t3, base + i * ctx.per, blk,
-                                     {n: grad_buf(t) for n, t in names.items()}, ws_ptr=wbase + i * stride,
-                                     reduce=False, weights=not batched)
-        if batched:
-            ops.preact_wide_wgrad_run(plan, gs.shape, run_ws, stride, *[list(v) for v in zip(*run)])
-        ops.preact_wide_reduce_run(plan, gs.shape, run_ws, stride)
-        grads_ready(plan.params)
-        return (ops.cast(gs, ctx.in_dtype), None) + (None,) * ctx.n_params
+class PreActStackFn(_RunFn):
+    """>= 2 blocks on a tiny grid: forward and backward in one launch each (preact_stack.hip)."""
+    run_fwd, run_bwd = staticmethod(ops.preact_stack_run_fwd), staticmethod(ops.preact_stack_run_bwd)
 
 
-class PreActMidRunFn(torch.autograd.Function):
-    """A run of 18-channel / branch-9 PreActFixupResBlocks (preact_mid.hip), chained: each block's
-    tile kernel also writes the next block's t2 (forward) / the previous block's gz3 (backward)
-    from the tile it holds in LDS, and the fixed-order gradient reductions of all blocks run as one
-    launch, so a run of n blocks costs n + 1 forward and 3n + 2 backward launches instead of 2n and
-    5n, and the out / gx round trips through the pointwise kernels are gone.  Numerics are the per-block path's (bit-identical t2 / gz3; only the scalar partial-sum
-    grouping of the fused stage differs)."""
-
-    @staticmethod
-    def forward(ctx, x, plan, *params):
-        ctx.n_params = len(params)
-        save = any(ctx.needs_input_grad)
-        out, saved = ops.preact_mid_run_fwd(x, plan.blocks, save=save)
-        ctx.plan = plan
-        if save:
-            ctx.save_for_backward(*[t for trio in saved for t in trio])
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        plan = ctx.plan
-        flat = ctx.saved_tensors
-        saved = [flat[3 * i: 3 * i + 3] for i in range(len(plan.blocks))]
-
-        gx = ops.preact_mid_run_bwd(g, plan, saved, on_done=lambda: grads_ready(plan.params))
-        return (gx, None) + (None,) * ctx.n_params
+class PreActWideFn(_RunFn):
+    """72-channel / branch-36 blocks, the run's weights packed once (preact_wide.hip)."""
+    run_fwd, run_bwd = staticmethod(ops.preact_wide_run_fwd), staticmethod(ops.preact_wide_run_bwd)
 
 
-class PreActSmallRunFn(torch.autograd.Function):
-    """A run of few-channel PreActFixupResBlocks ((C, branch) = (2, 1), (4, 2), (8, 4); preact_small.hip /
-    preact_col.hip): the fused forward per block, the fused backward per block into slices of one
-    run workspace, and the fixed-order gradient reductions of all blocks as one launch pair at the
-    end (instead of one or two small launches per block).  The residual stream between the run's
-    blocks is fp32 (ops.fp32_stream(); the reference's autocast blocks return fp32,
-    layers.py:187-193); the run returns its input's dtype, or fp32 when plan.out_dtype says so (the
-    encoder's pre-quantize runs feed the fp32 Quantizer, layers.py:685-687)."""
-
-    @staticmethod
-    def forward(ctx, x, plan, *params):
-        ctx.n_params = len(params)
-        save = any(ctx.needs_input_grad)
-        saved = []
-        n = len(plan.blocks)
-        last_dt = plan.out_dtype or x.dtype
-        odts = [last_dt if i == n - 1 else (torch.float32 if ops.fp32_stream() else x.dtype) for i in range(n)]
-        if ops.small_chain_ok(x, n):  # column kernels: each launch hands the next block its t2
-            x, runs = ops.preact_small_run_fwd(x, plan.blocks, save, odts)
-            saved = [t for r in runs for t in r]
-        else:
-            fmt = ops._fmt16(x)
-            for i, blk in enumerate(plan.blocks):
-                out, t2, t3 = ops.preact_small_fwd(x, blk, save=save, out_dtype=odts[i], fmt=fmt)
-                if save:
-                    saved += [x, t2, t3]
-                x = out
-        ctx.plan = plan
-        if save:
-            ctx.save_for_backward(*saved)
-        return x
-
-    @staticmethod
-    def backward(ctx, g):
-        plan = ctx.plan
-        flat = ctx.saved_tensors
-        saved = [flat[3 * i: 3 * i + 3] for i in range(len(plan.blocks))]
-        gx = ops.preact_small_run_bwd(g, plan, saved, on_done=lambda: grads_ready(plan.params))
-        return (gx, None) + (None,) * ctx.n_params
+class PreActMidRunFn(_RunFn):
+    """18-channel / branch-9 blocks, chained tile kernels (preact_mid.hip)."""
+    run_fwd, run_bwd = staticmethod(ops.preact_mid_run_fwd), staticmethod(ops.preact_mid_run_bwd)
 
 
-def small_run_eligible(x, blk):
-    k, s, _, up = mode_geometry(blk.mode)
-    return (stack_eligible(blk) and k == 3 and s == 1 and not up and x.is_cuda and x.dim() == 5
-            and x.shape[1] == blk.in_channels and ops.preact_small_supported(x, blk.branch_conv1.weight.shape[0])
-            and ops.small_backward_fused(x))
+class PreActSmallRunFn(_RunFn):
+    """Few-channel blocks, one reduction for the whole run (preact_small.hip / preact_col.hip)."""
+    run_fwd, run_bwd = staticmethod(ops.preact_small_plan_fwd), staticmethod(ops.preact_small_run_bwd)
 
 
-def mid_run_eligible(x, blk):
-    k, s, _, up = mode_geometry(blk.mode)
-    return (stack_eligible(blk) and k == 3 and s == 1 and not up and x.is_cuda and x.dim() == 5
-            and x.shape[1] == blk.in_channels and ops.preact_mid_supported(x, blk.branch_conv1.weight.shape[0]))
-
-
-def wide_eligible(x, blk):
-    return (stack_eligible(blk) and x.is_cuda and x.dim() == 5 and x.shape[1] == blk.in_channels
-            and ops.preact_wide_supported(x, blk.branch_conv1.weight.shape[0]))
-
-
-def stack_eligible(blk):
-    return (type(blk).__name__ == "PreActFixupResBlock" and blk.skip_conv is None and blk.mode in ("same", "out"))
+# run_route's answer -> the Function whose .apply runs it (vq3d.library's `kind` strings)
+RUN_FNS = {"stack": PreActStackFn, "wide": PreActWideFn, "mid": PreActMidRunFn, "small": PreActSmallRunFn}
 
 
 # ============================================================================================ generic conv

@@ -12,7 +12,6 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib as L
 from . import functional as Fn
 from .evonorm import EvoNorm3DS0
 from . import ops
@@ -232,11 +231,8 @@ class EvonormResBlock(nn.Module):
 # ============================================================================================ stacks
 class BlockStack(nn.Sequential):
     """nn.Sequential (same children, same state_dict keys) whose forward runs every maximal run of
-    identical PreActFixupResBlocks ('same', no skip) fused: >= 2 blocks on a tiny grid as ONE stack
-    (Fn.PreActStackFn: one launch forward, one backward), a run of 72-channel / branch-36 blocks
-    through Fn.PreActWideFn (preact_wide.hip), a run of 18-channel / branch-9 blocks chained through
-    Fn.PreActMidRunFn (preact_mid.hip), a run of few-channel blocks through Fn.PreActSmallRunFn
-    (one reduction for the whole run); everything else runs module by module."""
+    identical PreActFixupResBlocks ('same', no skip) fused, through the engine Fn.run_route names
+    (Fn.RUN_FNS: stack, wide, mid or small); everything else runs module by module."""
 
     out_fp32 = False  # set where the consumer takes an fp32 tensor (the encoder's Quantizers)
     small_runs_only = False  # Down / UpBlock: only few-channel runs fused (their fp32 stream)
@@ -245,26 +241,15 @@ class BlockStack(nn.Sequential):
         mods = list(self)
         i = 0
         while i < len(mods):
-            j = i
+            j, route = i, None
             if Fn.stack_eligible(mods[i]):
                 c, nb = mods[i].in_channels, mods[i].branch_conv1.weight.shape[0]
                 while (j + 1 < len(mods) and Fn.stack_eligible(mods[j + 1]) and mods[j + 1].in_channels == c
                        and mods[j + 1].branch_conv1.weight.shape[0] == nb):
                     j += 1
-            fn = None
-            if self.small_runs_only:
-                if j > i and Fn.small_run_eligible(x, mods[i]):
-                    fn = Fn.PreActSmallRunFn
-            elif Fn.stack_eligible(mods[i]):
-                if j > i and self._stack_ok(x, mods[i]):
-                    fn = Fn.PreActStackFn
-                elif Fn.wide_eligible(x, mods[i]):
-                    fn = Fn.PreActWideFn
-                elif j > i and Fn.mid_run_eligible(x, mods[i]):
-                    fn = Fn.PreActMidRunFn
-                elif j > i and Fn.small_run_eligible(x, mods[i]):
-                    fn = Fn.PreActSmallRunFn
-            if fn is not None:
+                if x.is_cuda:
+                    route = Fn.run_route(x.dtype, x.shape, mods[i], j - i + 1, self.small_runs_only)
+            if route is not None:
                 run = tuple(mods[i:j + 1])
                 plan = self._plans.get((i, j)) if hasattr(self, "_plans") else None
                 if plan is None or plan.blocks != list(run):
@@ -273,21 +258,13 @@ class BlockStack(nn.Sequential):
                     plan = self._plans[(i, j)] = Fn.StackPlan(run)
                 # the stack's last run hands an fp32 stream on when the consumer takes it
                 plan.out_dtype = torch.float32 if (self.out_fp32 and j == len(mods) - 1 and
-                                                   fn is Fn.PreActSmallRunFn and ops.fp32_stream()) else None
-                x = Fn.preact_run(fn, x, plan)
+                                                   route == "small" and ops.fp32_stream()) else None
+                x = Fn.preact_run(route, x, plan)
                 i = j + 1
             else:
                 x = mods[i](x)
                 i += 1
         return x
-
-    @staticmethod
-    def _stack_ok(x, blk):
-        if not (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16, torch.float16)):
-            return False
-        b, c, h, w, d = x.shape
-        return c == blk.in_channels and bool(L.query("vq3d_preact_stack_supported", b, c,
-                                                      blk.branch_conv1.weight.shape[0], h, w, d))
 
 
 class DownBlock(nn.Module):

@@ -25,9 +25,10 @@ Each operator runs exactly the kernels of the ctypes path (the same autograd.Fun
 vq3d.functional, driven through a stand-in context), so `vq3d.functional.set_binding("library")`
 gives a bit-identical step (tests/test_gpu_library.py).  Operator contracts:
   * a forward operator returns [outputs..., meta, saved...]: `meta` (int64, host) holds the path
-    flags the forward chose and, per saved tensor of the backward, a code: -1 none, k >= 0 the k-th
-    `saved` tensor, -2 - i the i-th of the forward's tensor inputs / outputs (outputs never alias
-    inputs, as torch.library requires);
+    tag the forward chose (PreActBlockFn's ctx.path as an index and ctx.fused_bwd; -1 elsewhere)
+    and, per saved tensor of the backward, a code: -1 none, k >= 0 the k-th `saved` tensor, -2 - i
+    the i-th of the forward's tensor inputs / outputs (outputs never alias inputs, as torch.library
+    requires);
   * a backward operator takes the resolved saved list and the parameter gradient buffers
     (`grads`, mutated: the kernels accumulate into them, `param.grad` of vq3d.flat) and returns
     [codes, new...] for the input gradients in the same encoding over its own tensor inputs;
@@ -42,13 +43,23 @@ from typing import List, Optional
 
 import torch
 
-from . import _lib as L
 from . import functional as Fn
 from . import ops
 from .ops import ConvGeom
 
 Tensor = torch.Tensor
-_FLAGS = ("tiny", "small", "mid")  # PreActBlockFn's path choice (the only forward-chosen state)
+_FLAGS = ("path", "fused_bwd")  # PreActBlockFn's path tag (the only forward-chosen state): meta's first ints
+_PATHS = ("tiny", "small", "mid", "convs")  # Fn.block_path's answers; meta holds the index
+
+
+def _tag(ctx):
+    """the forward context's path tag as ints (-1: not set, every Function but PreActBlockFn)"""
+    return [_PATHS.index(ctx.path) if hasattr(ctx, "path") else -1, int(getattr(ctx, "fused_bwd", -1))]
+
+
+def _untag(ctx, flags):
+    """_tag's ints back onto a backward's stand-in context"""
+    ctx.path, ctx.fused_bwd = _PATHS[flags[0]], flags[1] > 0
 
 
 # ------------------------------------------------------------------------------------------------ plumbing
@@ -106,13 +117,12 @@ def _forward(fn, nout, pool_in, needs, *args):
     res = fn.forward(ctx, *args)
     outs = list(res) if isinstance(res, tuple) else [res]
     assert len(outs) == nout
-    flags = [int(getattr(ctx, f)) if hasattr(ctx, f) else -1 for f in _FLAGS]
     codes, new = _pack(ctx.saved_tensors, pool_in + outs)
-    return outs + [torch.tensor(flags + codes, dtype=torch.int64)] + new
+    return outs + [torch.tensor(_tag(ctx) + codes, dtype=torch.int64)] + new
 
 
 def _saved(ctx, inputs, output, nout, pool_fn):
-    """setup_context helper: the backward's saved list and the forward's path flags."""
+    """setup_context helper: the backward's saved list and the forward's path tag."""
     outs, meta, new = list(output[:nout]), output[nout], list(output[nout + 1:])
     m = meta.tolist()
     ctx.flags = m[:len(_FLAGS)]
@@ -244,10 +254,6 @@ def _plan(params, out_fp32):
     return plan
 
 
-_RUNS = {"stack": Fn.PreActStackFn, "wide": Fn.PreActWideFn, "mid": Fn.PreActMidRunFn, "small": Fn.PreActSmallRunFn}
-RUN_KINDS = {v: k for k, v in _RUNS.items()}
-
-
 # ------------------------------------------------------------------------------------------------ conv3d
 def _spec(weight, scale, bias, cbias, pro, geom, residual_up2, post_elu):
     return Fn.ConvSpec(weight, ConvGeom(*geom), pro=tuple(pro) if pro else None, scale=scale, bias=bias,
@@ -321,9 +327,7 @@ def preact_block_backward(g: Tensor, saved: List[Optional[Tensor]], flags: List[
     _check_grads(params, grads)
     ctx = _Ctx()
     ctx.saved_tensors, ctx.blk, ctx.n_params = tuple(saved), _views(params, mode, len(params))[0][0], 0
-    for f, v in zip(_FLAGS, flags):
-        if v >= 0:
-            setattr(ctx, f, bool(v))
+    _untag(ctx, flags)
     return _backward(Fn.PreActBlockFn, ctx, [g], (g,))
 
 
@@ -350,23 +354,16 @@ def block(x, blk):
 
 @torch.library.custom_op("vq3d::preact_run", mutates_args=())
 def preact_run(x: Tensor, params: List[Tensor], kind: str, out_fp32: bool, save: bool) -> List[Tensor]:
-    return _forward(_RUNS[kind], 1, [x], (save,), x, _plan(params, out_fp32))
+    return _forward(Fn.RUN_FNS[kind], 1, [x], (save,), x, _plan(params, out_fp32))
 
 
 @torch.library.custom_op("vq3d::preact_run_backward", mutates_args=("grads",))
 def preact_run_backward(g: Tensor, saved: List[Optional[Tensor]], params: List[Tensor], kind: str, out_fp32: bool,
                         in_dtype: torch.dtype, grads: List[Tensor]) -> List[Tensor]:
     _check_grads(params, grads)
-    plan = _plan(params, out_fp32)
     ctx = _Ctx()
-    ctx.saved_tensors, ctx.plan, ctx.n_params = tuple(saved), plan, 0
-    nb, c = params[8].shape[0], params[8].shape[1]
-    if kind == "wide":  # PreActWideFn's per-block image stride and the run's input storage
-        ctx.per, ctx.in_dtype = int(L.query("vq3d_preact_wide_image_bytes", c, nb)), in_dtype
-    elif kind == "stack":
-        b, _, h, w, d = g.shape
-        ctx.shape = (b, c, nb, h, w, d)
-    return _backward(_RUNS[kind], ctx, [g], (g,))
+    ctx.saved_tensors, ctx.plan, ctx.in_dtype, ctx.n_params = tuple(saved), _plan(params, out_fp32), in_dtype, 0
+    return _backward(Fn.RUN_FNS[kind], ctx, [g], (g,))
 
 
 def _run_setup(ctx, inputs, output):
@@ -384,10 +381,10 @@ def _run_bwd(ctx, grads):
 _register("preact_run", _run_bwd, _run_setup, (0,))
 
 
-def run(fn, x, plan):
-    """A run Function (Fn.PreAct{Stack,Wide,MidRun,SmallRun}Fn) through the registered operator."""
+def run(kind, x, plan):
+    """A run Function (Fn.RUN_FNS[kind]) through the registered operator."""
     params = [p for b in plan.blocks for p in b._fn_params]
-    args = (x, params, RUN_KINDS[fn], plan.out_dtype is torch.float32, _save_flag(x, *params))
+    args = (x, params, kind, plan.out_dtype is torch.float32, _save_flag(x, *params))
     return _call("preact_run", args, (x,), params)[0]
 
 
@@ -622,7 +619,7 @@ def recon_loss(dec, x, nvs, cylinder, *commit):
 # Shape / dtype / stride propagation for tracing (torch.compile, torch.export): every operator has
 # a fake implementation.  The forward operators' outputs are [result(s), meta, saved...]: with
 # save=False (inference: eval / torch.no_grad, what a traced deployment runs) no intermediate is
-# saved and the structure is fixed, [result, meta (3 path flags)].  With save=True the saved set
+# saved and the structure is fixed, [result, meta (the path tag)].  With save=True the saved set
 # depends on the engine the forward picks at run time (tiny / few-channel / mid / per-conv paths),
 # so a training-mode forward is not traceable: its fake says so.  The backward operators (called by
 # the registered autograd formulas only) return engine-dependent lists too and are likewise

@@ -352,39 +352,94 @@ def preact_tiny_supported(x_shape, branch):
     return bool(L.query("vq3d_preact_tiny_supported", b, c, branch, h, w, d))
 
 
+# ------------------------------------------------------------------------------------------------ block call glue
+# A block's 11 parameters (attribute names) in the ONE order shared by L.PreactGrads._fields_, the
+# run tables (functional.StackPlan: [block][11]) and vq3d_preact_stack_fwd.
+PRM = ("branch_conv1", "branch_conv2", "branch_conv3", "bias1a", "bias1b", "bias2a", "bias2b", "bias3a", "bias3b",
+       "scale", "bias4")
+
+
+def block_params(blk):
+    """The block's 11 parameter tensors, in PRM order."""
+    return [getattr(blk, n).weight if n.startswith("branch_conv") else getattr(blk, n) for n in PRM]
+
+
+def grad_buf(p):
+    """fp32 gradient buffer of parameter p (allocated zeroed if the caller set it to None)."""
+    if p is None:
+        return None
+    if p.grad is None:
+        p.grad = zero_(torch.empty_like(p))
+    return p.grad
+
+
+def block_grads(blk):
+    """{L.PreactGrads field: the parameter's gradient buffer} of one block."""
+    return {f: grad_buf(t) for (f, _), t in zip(L.PreactGrads._fields_, block_params(blk))}
+
+
 def _preact_params(blk):
-    return L.PreactParams(*[_p(getattr(blk, n)) for n in ("bias1a", "bias1b", "bias2a", "bias2b", "bias3a",
-                                                            "bias3b", "scale", "bias4")])
+    return L.PreactParams(*[_p(getattr(blk, n)) for n in PRM[3:]])
+
+
+def _block(blk):
+    """A block's launch preamble: branch width, the three weight pointers, its PreactParams."""
+    w1 = blk.branch_conv1.weight
+    return (w1.shape[0], L.ptr(w1), L.ptr(blk.branch_conv2.weight), L.ptr(blk.branch_conv3.weight),
+            _preact_params(blk))
+
+
+def _grads(grads):
+    """L.PreactGrads from {field: fp32 buffer (+=)} or from a run plan's grad_ptrs(i) (addresses in
+    field order)."""
+    if isinstance(grads, dict):
+        return L.PreactGrads(*[_p(grads.get(n)) for n, _ in L.PreactGrads._fields_])
+    return L.PreactGrads(*[ctypes.c_void_p(int(gp)) for gp in grads])
+
+
+def run_workspace(nbytes_per_block, nblocks, device):
+    """One backward workspace for a run, a 256-byte aligned slice per block: (buffer, base address,
+    per-block stride)."""
+    stride = (int(nbytes_per_block) + 255) // 256 * 256
+    buf = workspace(stride * nblocks, device)
+    return buf, buf.data_ptr(), stride
+
+
+def to_cl(g):
+    """An incoming gradient in channels-last layout (a copy only when autograd hands another)."""
+    if g.is_contiguous(memory_format=CL) or (g.shape[1] == 1 and g.is_contiguous()):
+        return g
+    return g.contiguous(memory_format=CL)
+
+
+def _trios(flat, n):
+    """a run's flat saved list as per-block (x_i, t2_i, t3_i)"""
+    return [flat[3 * i: 3 * i + 3] for i in range(n)]
 
 
 def preact_tiny_fwd(x, blk):
     """Whole PreActFixupResBlock ('same', no skip) in one kernel on a tiny grid (vq3d.h)."""
     x = as_cl(x)
     b, c, h, w, d = x.shape
-    w1, w2, w3 = blk.branch_conv1.weight, blk.branch_conv2.weight, blk.branch_conv3.weight
+    nb, w1, w2, w3, prm = _block(blk)
     out = torch.empty_like(x, memory_format=CL)
-    nb = w1.shape[0]
     saved = torch.empty(L.query("vq3d_preact_tiny_saved_floats", b, nb, h, w, d), dtype=torch.float32,
                         device=x.device)
-    prm = _preact_params(blk)
-    L.call("vq3d_preact_tiny_fwd", L.dtype_code(x), b, c, nb, h, w, d, L.ptr(x), L.ptr(w1), L.ptr(w2),
-           L.ptr(w3), ctypes.byref(prm), L.ptr(out), L.ptr(saved), L.stream())
+    L.call("vq3d_preact_tiny_fwd", L.dtype_code(x), b, c, nb, h, w, d, L.ptr(x), w1, w2, w3, ctypes.byref(prm),
+           L.ptr(out), L.ptr(saved), L.stream())
     return out, saved
 
 
 def preact_tiny_bwd(g, x, saved, blk, grads):
     """gx of preact_tiny_fwd; grads: dict name -> fp32 buffer (+=), names as in L.PreactGrads."""
     b, c, h, w, d = x.shape
-    w1, w2, w3 = blk.branch_conv1.weight, blk.branch_conv2.weight, blk.branch_conv3.weight
-    nb = w1.shape[0]
+    nb, w1, w2, w3, prm = _block(blk)
     gx = torch.empty_like(x, memory_format=CL)
     ws = torch.empty(L.query("vq3d_preact_tiny_workspace_floats", b, nb, h, w, d), dtype=torch.float32,
                      device=x.device)
-    prm = _preact_params(blk)
-    gr = L.PreactGrads(*[_p(grads.get(n)) for n, _ in L.PreactGrads._fields_])
-    L.call("vq3d_preact_tiny_bwd", L.dtype_code(x), b, c, nb, h, w, d, L.ptr(x), L.ptr(g), L.ptr(w1),
-           L.ptr(w2), L.ptr(w3), ctypes.byref(prm), ctypes.byref(gr), L.ptr(saved), L.ptr(ws), L.ptr(gx),
-           L.stream())
+    gr = _grads(grads)
+    L.call("vq3d_preact_tiny_bwd", L.dtype_code(x), b, c, nb, h, w, d, L.ptr(x), L.ptr(g), w1, w2, w3,
+           ctypes.byref(prm), ctypes.byref(gr), L.ptr(saved), L.ptr(ws), L.ptr(gx), L.stream())
     return gx
 
 
@@ -415,9 +470,13 @@ def set_mid_blocks(enabled):
     _mid[0] = bool(enabled)
 
 
+def mid_supported(dtype, shape, branch):
+    b, c, h, w, d = shape
+    return _mid[0] and bool(L.query("vq3d_preact_mid_supported", L.dtype_code(dtype), b, c, branch, h, w, d))
+
+
 def preact_mid_supported(x, branch):
-    b, c, h, w, d = x.shape
-    return _mid[0] and bool(L.query("vq3d_preact_mid_supported", L.dtype_code(x), b, c, branch, h, w, d))
+    return mid_supported(x.dtype, x.shape, branch)
 
 
 def preact_mid_fwd(x, blk, stages=None, bufs=None, save=True):
@@ -426,16 +485,14 @@ def preact_mid_fwd(x, blk, stages=None, bufs=None, save=True):
     (vq3d_preact_mid_fwd_stages, preallocated outputs)."""
     x = as_cl(x)
     b, c, h, w, d = x.shape
-    w1, w2, w3 = blk.branch_conv1.weight, blk.branch_conv2.weight, blk.branch_conv3.weight
-    nb = w1.shape[0]
+    nb, w1, w2, w3, prm = _block(blk)
     if bufs is None:
         out = torch.empty_like(x, memory_format=CL)
         t2 = new_act(b, nb, h, w, d, x.dtype, x.device)
         t3 = new_act(b, nb, h, w, d, x.dtype, x.device) if save else None
     else:
         out, t2, t3 = bufs
-    prm = _preact_params(blk)
-    args = (L.dtype_code(x), b, c, nb, h, w, d, L.ptr(x), L.ptr(w1), L.ptr(w2), L.ptr(w3), ctypes.byref(prm),
+    args = (L.dtype_code(x), b, c, nb, h, w, d, L.ptr(x), w1, w2, w3, ctypes.byref(prm),
             L.ptr(out), L.ptr(t2), _p(t3), L.stream())
     if stages is None:
         L.call("vq3d_preact_mid_fwd", *args)
@@ -449,107 +506,91 @@ def preact_mid_bwd(g, x, t2, t3, blk, grads, stages=None, bufs=None):
     L.PreactGrads.  stages / bufs: measurement only (vq3d_preact_mid_bwd_stages, preallocated
     gx and workspace)."""
     b, c, h, w, d = x.shape
-    w1, w2, w3 = blk.branch_conv1.weight, blk.branch_conv2.weight, blk.branch_conv3.weight
-    nb = w1.shape[0]
+    nb, w1, w2, w3, prm = _block(blk)
     if bufs is None:
         gx = torch.empty_like(x, memory_format=CL)
         ws = workspace(L.query("vq3d_preact_mid_workspace_bytes", b, h, w, d), x.device)
     else:
         gx, ws = bufs
-    prm = _preact_params(blk)
-    gr = L.PreactGrads(*[_p(grads.get(n)) for n, _ in L.PreactGrads._fields_])
-    args = (L.dtype_code(x), b, c, nb, h, w, d, L.ptr(g), L.ptr(x), L.ptr(t2), L.ptr(t3), L.ptr(w1), L.ptr(w2),
-            L.ptr(w3), ctypes.byref(prm), ctypes.byref(gr), L.ptr(ws), ctypes.c_size_t(ws.numel()), L.ptr(gx))
+    gr = _grads(grads)
+    args = (L.dtype_code(x), b, c, nb, h, w, d, L.ptr(g), L.ptr(x), L.ptr(t2), L.ptr(t3), w1, w2, w3,
+            ctypes.byref(prm), ctypes.byref(gr), L.ptr(ws), ctypes.c_size_t(ws.numel()), L.ptr(gx))
     if stages is not None:
         L.call("vq3d_preact_mid_bwd_stages", int(stages), *args, L.stream())
     elif _concurrent:
         # data stages (gz3, gx; gz1 to the workspace) on the main stream, the weight gradient and
         # the fixed-order reduction on the side stream (they read g / x / t2 / t3 / workspace only)
         L.call("vq3d_preact_mid_bwd_stages", 3, *args, L.stream())
-        main = torch.cuda.current_stream()
-        side = _side_stream(x.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            L.call("vq3d_preact_mid_bwd_stages", 28, *args, L.stream())
-        for t in (g, x, t2, t3, ws):
-            t.record_stream(side)
+        _on_side(x.device, lambda: L.call("vq3d_preact_mid_bwd_stages", 28, *args, L.stream()), g, x, t2, t3, ws)
     else:
         L.call("vq3d_preact_mid_bwd", *args, L.stream())
     return gx
 
 
-def preact_mid_run_fwd(x, blocks, save=True):
-    """A RUN of fused mid-level blocks, chained (vq3d_preact_mid_fwd_chain): the first block's t2
-    stage, then one tile launch per block that also writes the next block's t2 from its out while
-    the tile is in LDS.  Returns out and, per block, (x_i, t2_i, t3_i) (t3_i None when save=False:
-    no backward follows)."""
+def preact_mid_run_fwd(x, plan, save=True):
+    """A RUN of 18-channel / branch-9 blocks, chained (vq3d_preact_mid_fwd_chain): the first block's
+    t2 stage, then one tile launch per block that also writes the next block's t2 from its out while
+    the tile is in LDS, so n blocks cost n + 1 launches instead of 2n and the out round trips through
+    the pointwise kernels are gone.  Numerics are the per-block path's (bit-identical t2).  Returns
+    out and the saved list, per block x_i, t2_i, t3_i (empty when save=False: no backward follows)."""
+    blocks = plan.blocks
     x = as_cl(x)
     b, c, h, w, d = x.shape
-    nb = blocks[0].branch_conv1.weight.shape[0]
     dc = L.dtype_code(x)
-    b0 = blocks[0]
+    pre = [_block(blk) for blk in blocks] + [None]
+    nb, w1, w2, w3, prm = pre[0]
     t2 = new_act(b, nb, h, w, d, x.dtype, x.device)
     out = torch.empty_like(x, memory_format=CL)
-    prm = _preact_params(b0)
-    L.call("vq3d_preact_mid_fwd_stages", 1, dc, b, c, nb, h, w, d, L.ptr(x), L.ptr(b0.branch_conv1.weight),
-           L.ptr(b0.branch_conv2.weight), L.ptr(b0.branch_conv3.weight), ctypes.byref(prm), L.ptr(out), L.ptr(t2),
-           None, L.stream())
+    L.call("vq3d_preact_mid_fwd_stages", 1, dc, b, c, nb, h, w, d, L.ptr(x), w1, w2, w3, ctypes.byref(prm),
+           L.ptr(out), L.ptr(t2), None, L.stream())
     saved = []
-    for i, blk in enumerate(blocks):
-        nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+    for i in range(len(blocks)):
+        (_, _, w2, w3, prm), nxt = pre[i], pre[i + 1]
         if i:
             out = torch.empty_like(x, memory_format=CL)
         t3 = new_act(b, nb, h, w, d, x.dtype, x.device) if save else None
         t2n = new_act(b, nb, h, w, d, x.dtype, x.device) if nxt is not None else None
-        prm = _preact_params(blk)
-        prmn = _preact_params(nxt) if nxt is not None else None
-        fargs = (dc, b, c, nb, h, w, d, L.ptr(x), L.ptr(blk.branch_conv2.weight), L.ptr(blk.branch_conv3.weight),
-                 ctypes.byref(prm), L.ptr(t2), L.ptr(out), _p(t3),
-                 None if nxt is None else L.ptr(nxt.branch_conv1.weight),
-                 None if prmn is None else ctypes.byref(prmn), _p(t2n), L.stream())
+        fargs = (dc, b, c, nb, h, w, d, L.ptr(x), w2, w3, ctypes.byref(prm), L.ptr(t2), L.ptr(out), _p(t3),
+                 None if nxt is None else nxt[1], None if nxt is None else ctypes.byref(nxt[4]), _p(t2n), L.stream())
         # k_pm_fwd<..., true> (the chained tile kernel) is the launch of every block but the last
         _timed("k_pm_fwd" if nxt is not None else "", lambda a=fargs: L.call("vq3d_preact_mid_fwd_chain", *a))
         if save:
-            saved.append((x, t2, t3))
+            saved += [x, t2, t3]
         x, t2 = out, t2n
     return x, saved
 
 
-def preact_mid_run_bwd(g, plan, saved, on_done=None):
+def preact_mid_run_bwd(g, plan, saved, in_dtype=None):
     """Backward of preact_mid_run_fwd (vq3d_preact_mid_bwd_chain): per block, in reverse, the data
     tile kernel also computes the PREVIOUS block's pointwise gz3 stage from its gx, and the weight
     gradient kernels follow (on the side stream in concurrent weight-gradient mode); every block's
     workspace is a slice of one run buffer, so the fixed-order reductions of all blocks run as ONE
-    launch at the end (vq3d_preact_mid_reduce_run, plan's device tables).  Returns gx of the run's
-    input; on_done() runs once the reduction is enqueued."""
+    launch at the end (vq3d_preact_mid_reduce_run, plan's device tables): 3n + 2 launches instead of
+    5n (bit-identical gz3; only the scalar partial-sum grouping of the fused stage differs from the
+    per-block path).  Returns gx of the run's input."""
     blocks = plan.blocks
-    g = g if g.is_contiguous(memory_format=CL) else g.contiguous(memory_format=CL)
+    saved = _trios(saved, len(blocks))
+    g = to_cl(g)
     b, c, h, w, d = g.shape
-    nb = blocks[0].branch_conv1.weight.shape[0]
     dc = L.dtype_code(g)
     nws = int(L.query("vq3d_preact_mid_workspace_bytes", b, h, w, d))
-    stride = (nws + 255) // 256 * 256
-    run_ws = workspace(stride * len(blocks), g.device)
-    base = run_ws.data_ptr()
+    run_ws, base, stride = run_workspace(nws, len(blocks), g.device)
     ptab, gtab = plan.tables(g.device)
     run_g = []  # batched weight gradients: every block's incoming gradient, kept for the run launch
     for i in reversed(range(len(blocks))):
-        blk = blocks[i]
         x, t2, t3 = saved[i]
         gx = torch.empty_like(x, memory_format=CL)
-        prm = _preact_params(blk)
-        gr = L.PreactGrads(*[ctypes.c_void_p(int(gp)) for gp in plan.grad_ptrs(i)])
+        nb, w1, w2, w3, prm = _block(blocks[i])
+        gr = _grads(plan.grad_ptrs(i))
         if i:
-            prev = blocks[i - 1]
-            prmp = _preact_params(prev)
-            chain = (L.ptr(saved[i - 1][2]), L.ptr(prev.branch_conv3.weight), ctypes.byref(prmp),
-                     ctypes.c_void_p(base + (i - 1) * stride), ctypes.c_size_t(nws))
+            _, _, _, pw3, prmp = _block(blocks[i - 1])
+            chain = (L.ptr(saved[i - 1][2]), pw3, ctypes.byref(prmp), ctypes.c_void_p(base + (i - 1) * stride),
+                     ctypes.c_size_t(nws))
         else:
             chain = (None, None, None, None, ctypes.c_size_t(0))
         first = 1 if i == len(blocks) - 1 else 0
-        args = (dc, b, c, nb, h, w, d, L.ptr(g), L.ptr(x), L.ptr(t2), L.ptr(t3), L.ptr(blk.branch_conv1.weight),
-                L.ptr(blk.branch_conv2.weight), L.ptr(blk.branch_conv3.weight), ctypes.byref(prm), ctypes.byref(gr),
-                ctypes.c_void_p(base + i * stride), ctypes.c_size_t(nws), L.ptr(gx))
+        args = (dc, b, c, nb, h, w, d, L.ptr(g), L.ptr(x), L.ptr(t2), L.ptr(t3), w1, w2, w3, ctypes.byref(prm),
+                ctypes.byref(gr), ctypes.c_void_p(base + i * stride), ctypes.c_size_t(nws), L.ptr(gx))
         if _concurrent:
             L.call("vq3d_preact_mid_bwd_chain", first | 2, *args, *chain, L.stream())
             _on_side(g.device, lambda a=args: L.call("vq3d_preact_mid_bwd_stages", 12, *a, L.stream()),
@@ -569,21 +610,22 @@ def preact_mid_run_bwd(g, plan, saved, on_done=None):
             L.call("vq3d_preact_mid_bwd_chain", first | 14, *args, *chain, L.stream())
         g = gx
     if run_g:
-        n = len(blocks)
-        arr = ctypes.c_void_p * n
         run_g.reverse()  # run_g[i]: block i's incoming gradient
-        L.call("vq3d_preact_mid_wgrad_run", dc, n, b, h, w, d, arr(*[s_[1].data_ptr() for s_ in saved]),
-               arr(*[s_[2].data_ptr() for s_ in saved]), arr(*[s_[0].data_ptr() for s_ in saved]),
-               arr(*[t.data_ptr() for t in run_g]), L.ptr(ptab), ctypes.c_void_p(base), ctypes.c_size_t(stride),
-               L.stream())
+        L.call("vq3d_preact_mid_wgrad_run", dc, len(blocks), b, h, w, d, _ptrs(s_[1] for s_ in saved),
+               _ptrs(s_[2] for s_ in saved), _ptrs(s_[0] for s_ in saved), _ptrs(run_g), L.ptr(ptab),
+               ctypes.c_void_p(base), ctypes.c_size_t(stride), L.stream())
     red = (len(blocks), b, h, w, d, ctypes.c_void_p(base), ctypes.c_size_t(stride), L.ptr(gtab), L.ptr(ptab))
     if _concurrent:
         _on_side(g.device, lambda: L.call("vq3d_preact_mid_reduce_run", *red, L.stream()), run_ws, ptab, gtab)
     else:
         L.call("vq3d_preact_mid_reduce_run", *red, L.stream())
-    if on_done is not None:
-        on_done()
     return g
+
+
+def _ptrs(tensors):
+    """a host array of the tensors' device addresses (the run launches' per-block pointer lists)"""
+    ps = [t.data_ptr() for t in tensors]
+    return (ctypes.c_void_p * len(ps))(*ps)
 
 
 def _on_side(device, fn, *keep):
@@ -617,8 +659,8 @@ def set_small_blocks(enabled, fused_backward=True):
 _SMALL_BWD_MAX_VOX = 1 << 19
 
 
-def small_backward_fused(x):
-    b, c, h, w, d = x.shape
+def small_bwd_fused(shape):
+    b, c, h, w, d = shape
     if not _small[1]:
         return False
     nb = c // 2
@@ -627,9 +669,17 @@ def small_backward_fused(x):
     return b * h * w * d <= _SMALL_BWD_MAX_VOX
 
 
+def small_backward_fused(x):
+    return small_bwd_fused(x.shape)
+
+
+def small_supported(dtype, shape, branch):
+    b, c, h, w, d = shape
+    return _small[0] and bool(L.query("vq3d_preact_small_supported", L.dtype_code(dtype), b, c, branch, h, w, d))
+
+
 def preact_small_supported(x, branch):
-    b, c, h, w, d = x.shape
-    return _small[0] and bool(L.query("vq3d_preact_small_supported", L.dtype_code(x), b, c, branch, h, w, d))
+    return small_supported(x.dtype, x.shape, branch)
 
 
 _fp32_stream = [True]
@@ -658,15 +708,13 @@ def preact_small_fwd(x, blk, save=True, out_dtype=None, fmt=None):
     x = as_cl(x)
     b, c, h, w, d = x.shape
     fmt = fmt or _fmt16(x)
-    w1, w2, w3 = blk.branch_conv1.weight, blk.branch_conv2.weight, blk.branch_conv3.weight
-    nb = w1.shape[0]
+    nb, w1, w2, w3, prm = _block(blk)
     out = torch.empty_like(x, memory_format=CL, dtype=out_dtype or x.dtype)
     t2 = new_act(b, nb, h, w, d, fmt, x.device) if save else None
     t3 = new_act(b, nb, h, w, d, fmt, x.device) if save else None
-    prm = _preact_params(blk)
     _timed(lambda: _small_kind("fwd", b, c, nb, h, w, d), lambda: L.call(
         "vq3d_preact_small_fwd_io", L.dtype_code(fmt), L.dtype_code(x), L.dtype_code(out), b, c, nb, h, w, d,
-        L.ptr(x), L.ptr(w1), L.ptr(w2), L.ptr(w3), ctypes.byref(prm), L.ptr(out), _p(t2), _p(t3), L.stream()))
+        L.ptr(x), w1, w2, w3, ctypes.byref(prm), L.ptr(out), _p(t2), _p(t3), L.stream()))
     return out, t2, t3
 
 
@@ -692,22 +740,20 @@ def preact_small_run_fwd(x, blocks, save, out_dtypes):
     x = as_cl(x)
     b, c, h, w, d = x.shape
     fmt = _fmt16(x)
-    nb = blocks[0].branch_conv1.weight.shape[0]
     n = len(blocks)
+    pre = [_block(blk) for blk in blocks] + [None]
+    nb = pre[0][0]
     saved = []
     t2 = new_act(b, nb, h, w, d, fmt, x.device)
-    prms = [_preact_params(blk) for blk in blocks]
-    for i, blk in enumerate(blocks):
+    for i in range(n):
+        (_, w1, w2, w3, prm), nxt = pre[i], pre[i + 1]
         out = torch.empty_like(x, memory_format=CL, dtype=out_dtypes[i])
         t3 = new_act(b, nb, h, w, d, fmt, x.device) if save else None
-        t2n = new_act(b, nb, h, w, d, fmt, x.device) if i + 1 < n else None
-        mode = (1 if i else 0) | (2 if i + 1 < n else 0)
-        nxt = blocks[i + 1] if i + 1 < n else None
+        t2n = new_act(b, nb, h, w, d, fmt, x.device) if nxt is not None else None
+        mode = (1 if i else 0) | (2 if nxt is not None else 0)
         args = (mode, L.dtype_code(fmt), L.dtype_code(x), L.dtype_code(out), b, c, nb, h, w, d, L.ptr(x),
-                L.ptr(t2) if i else None, L.ptr(blk.branch_conv1.weight), L.ptr(blk.branch_conv2.weight),
-                L.ptr(blk.branch_conv3.weight), ctypes.byref(prms[i]), L.ptr(out), L.ptr(t2), _p(t3),
-                _p(nxt.branch_conv1.weight) if nxt is not None else None,
-                ctypes.byref(prms[i + 1]) if nxt is not None else None, _p(t2n), L.stream())
+                L.ptr(t2) if i else None, w1, w2, w3, ctypes.byref(prm), L.ptr(out), L.ptr(t2), _p(t3),
+                None if nxt is None else nxt[1], None if nxt is None else ctypes.byref(nxt[4]), _p(t2n), L.stream())
         _timed(lambda: _small_kind("fwd", b, c, nb, h, w, d),
                lambda a=args: L.call("vq3d_preact_small_fwd_chain", *a))
         if save:
@@ -716,58 +762,74 @@ def preact_small_run_fwd(x, blocks, save, out_dtypes):
     return x, saved
 
 
+def preact_small_plan_fwd(x, plan, save=True):
+    """A RUN of few-channel blocks ((C, branch) = (2, 1), (4, 2), (8, 4); preact_small.hip /
+    preact_col.hip): the fused forward per block, chained (preact_small_run_fwd) where the column
+    kernels apply.  The residual stream between the run's blocks is fp32 (fp32_stream(); the
+    reference's autocast blocks return fp32, layers.py:187-193); the run returns its input's dtype,
+    or fp32 when plan.out_dtype says so (the encoder's pre-quantize runs feed the fp32 Quantizer,
+    layers.py:685-687).  Returns out and the saved list, per block x_i, t2_i, t3_i."""
+    blocks = plan.blocks
+    n = len(blocks)
+    mid_dt = torch.float32 if _fp32_stream[0] else x.dtype
+    odts = [mid_dt] * (n - 1) + [plan.out_dtype or x.dtype]
+    if small_chain_ok(x, n):  # column kernels: each launch hands the next block its t2
+        x, trios = preact_small_run_fwd(x, blocks, save, odts)
+        return x, [t for trio in trios for t in trio]
+    saved = []
+    fmt = _fmt16(x)
+    for i, blk in enumerate(blocks):
+        out, t2, t3 = preact_small_fwd(x, blk, save=save, out_dtype=odts[i], fmt=fmt)
+        if save:
+            saved += [x, t2, t3]
+        x = out
+    return x, saved
+
+
 def preact_small_bwd(g, x, t2, t3, blk, grads):
     """gx of preact_small_fwd; grads: dict name -> fp32 buffer (+=), names as in L.PreactGrads."""
     b, c, h, w, d = x.shape
-    w1, w2, w3 = blk.branch_conv1.weight, blk.branch_conv2.weight, blk.branch_conv3.weight
-    nb = w1.shape[0]
+    nb, w1, w2, w3, prm = _block(blk)
     gx = torch.empty_like(x, memory_format=CL)
     nbytes = L.query("vq3d_preact_small_workspace_bytes", b, c, nb, h, w, d)
     ws = workspace(nbytes, x.device)
-    prm = _preact_params(blk)
-    gr = L.PreactGrads(*[_p(grads.get(n)) for n, _ in L.PreactGrads._fields_])
-    args = (L.dtype_code(x), b, c, nb, h, w, d, L.ptr(g), L.ptr(x), L.ptr(t2), L.ptr(t3), L.ptr(w1), L.ptr(w2),
-            L.ptr(w3), ctypes.byref(prm), ctypes.byref(gr), L.ptr(ws), ctypes.c_size_t(ws.numel()), L.ptr(gx))
+    gr = _grads(grads)
+    args = (L.dtype_code(x), b, c, nb, h, w, d, L.ptr(g), L.ptr(x), L.ptr(t2), L.ptr(t3), w1, w2, w3,
+            ctypes.byref(prm), ctypes.byref(gr), L.ptr(ws), ctypes.c_size_t(ws.numel()), L.ptr(gx))
     L.call("vq3d_preact_small_bwd", *args, L.stream())
     return gx
 
 
-def preact_small_run_bwd(g, plan, saved, on_done=None):
+def preact_small_run_bwd(g, plan, saved, in_dtype=None):
     """Backward of a run of fused few-channel blocks: per block, in reverse, the fused data /
     partial-sum kernel into its slice of one run workspace, then the fixed-order reductions of every
-    block as one launch pair (vq3d_preact_small_reduce_run, plan's device tables).  Each block's g
-    has its out's storage and its gx its input's (the fp32 stream inside the run).  (A backward
-    chained like the forward -- each launch forming the previous block's gz3 in its epilogue --
-    was measured slower: the epilogue's extra registers cost more than the halo math it saves.)
-    Returns gx of the run's input."""
+    block as one launch pair (vq3d_preact_small_reduce_run, plan's device tables) instead of one or
+    two small launches per block.  Each block's g has its out's storage and its gx its input's (the
+    fp32 stream inside the run).  (A backward chained like the forward -- each launch forming the
+    previous block's gz3 in its epilogue -- was measured slower: the epilogue's extra registers cost
+    more than the halo math it saves.)  Returns gx of the run's input."""
     blocks = plan.blocks
-    g = g if g.is_contiguous(memory_format=CL) else g.contiguous(memory_format=CL)
+    saved = _trios(saved, len(blocks))
+    g = to_cl(g)
     b, c, h, w, d = g.shape
     nb = blocks[0].branch_conv1.weight.shape[0]
     fmt = saved[0][1].dtype
     nws = int(L.query("vq3d_preact_small_workspace_bytes", b, c, nb, h, w, d))
-    stride = (nws + 255) // 256 * 256
-    run_ws = workspace(stride * len(blocks), g.device)
-    base = run_ws.data_ptr()
+    run_ws, base, stride = run_workspace(nws, len(blocks), g.device)
     ptab, gtab = plan.tables(g.device)
-    run_g = []  # batched weight gradients: every block's incoming gradient, kept for the run launch
     for i in reversed(range(len(blocks))):
-        blk = blocks[i]
         x, t2, t3 = saved[i]
         gx = torch.empty_like(x, memory_format=CL)
-        prm = _preact_params(blk)
-        gr = L.PreactGrads(*[ctypes.c_void_p(int(gp)) for gp in plan.grad_ptrs(i)])
+        _, w1, w2, w3, prm = _block(blocks[i])
+        gr = _grads(plan.grad_ptrs(i))
         sargs = (L.dtype_code(fmt), L.dtype_code(x), L.dtype_code(g), b, c, nb, h, w, d, L.ptr(g), L.ptr(x),
-                 L.ptr(t2), L.ptr(t3), L.ptr(blk.branch_conv1.weight), L.ptr(blk.branch_conv2.weight),
-                 L.ptr(blk.branch_conv3.weight), ctypes.byref(prm), ctypes.byref(gr),
+                 L.ptr(t2), L.ptr(t3), w1, w2, w3, ctypes.byref(prm), ctypes.byref(gr),
                  ctypes.c_void_p(base + i * stride), ctypes.c_size_t(nws), L.ptr(gx), L.stream())
         _timed(lambda: _small_kind("bwd", b, c, nb, h, w, d),
                lambda a=sargs: L.call("vq3d_preact_small_bwd_stages_io", 1, *a))
         g = gx
     L.call("vq3d_preact_small_reduce_run", len(blocks), b, c, nb, h, w, d, ctypes.c_void_p(base),
            ctypes.c_size_t(stride), L.ptr(gtab), L.ptr(ptab), L.stream())
-    if on_done is not None:
-        on_done()
     return g
 
 
@@ -780,10 +842,14 @@ def set_wide_blocks(enabled):
     _wide[0] = bool(enabled)
 
 
-def preact_wide_supported(x, branch):
-    b, c, h, w, d = x.shape
-    return (_wide[0] and x.dtype in (torch.bfloat16, torch.float16)
+def wide_supported(dtype, shape, branch):
+    b, c, h, w, d = shape
+    return (_wide[0] and dtype in (torch.bfloat16, torch.float16)
             and bool(L.query("vq3d_preact_wide_supported", b, c, branch, h, w, d)))
+
+
+def preact_wide_supported(x, branch):
+    return wide_supported(x.dtype, x.shape, branch)
 
 
 def preact_wide_pack(ptab, nblocks, c, nb, device, dtype=torch.bfloat16):
@@ -804,8 +870,8 @@ def preact_wide_fwd(x32, img_ptr, blk, save=True, dtype=torch.bfloat16):
     t2 = new_act(b, nb, h, w, d, dtype, x32.device) if save else None
     t3 = new_act(b, nb, h, w, d, dtype, x32.device) if save else None
     prm = _preact_params(blk)
-    L.call("vq3d_preact_wide_fwd", L.dtype_code(dtype), b, c, nb, h, w, d, L.ptr(x32), ctypes.c_void_p(img_ptr), ctypes.byref(prm),
-           L.ptr(out), _p(t2), _p(t3), L.stream())
+    L.call("vq3d_preact_wide_fwd", L.dtype_code(dtype), b, c, nb, h, w, d, L.ptr(x32), ctypes.c_void_p(img_ptr),
+           ctypes.byref(prm), L.ptr(out), _p(t2), _p(t3), L.stream())
     return out, t2, t3
 
 
@@ -830,7 +896,7 @@ def preact_wide_bwd(g32, x32, t2, t3, img_ptr, blk, grads, ws_ptr=None, reduce=T
            ctypes.c_void_p(img_ptr), ctypes.byref(prm), wsp, ctypes.c_size_t(nws), L.ptr(gx), L.stream())
     if not weights:
         return gx
-    gr = L.PreactGrads(*[_p(grads.get(n)) for n, _ in L.PreactGrads._fields_])
+    gr = _grads(grads)
     args = (1 | (2 if reduce else 0), dc, b, c, nb, h, w, d, L.ptr(g32), L.ptr(x32), L.ptr(t2), L.ptr(t3),
             ctypes.byref(prm), ctypes.byref(gr), wsp, ctypes.c_size_t(nws))
     if _concurrent:
@@ -841,36 +907,94 @@ def preact_wide_bwd(g32, x32, t2, t3, img_ptr, blk, grads, ws_ptr=None, reduce=T
     return gx
 
 
-def preact_wide_run_workspace(plan, shape, device):
-    """One workspace for a run of wide blocks: (buffer, base address, per-block stride)."""
-    b, c, h, w, d = shape
-    nws = int(L.query("vq3d_preact_wide_workspace_bytes", b, h, w, d))
-    stride = (nws + 255) // 256 * 256
-    buf = workspace(stride * len(plan.blocks), device)
-    return buf, buf.data_ptr(), stride
+def preact_wide_run_fwd(x, plan, save=True):
+    """A RUN of 72-channel / branch-36 blocks (preact_wide.hip): the weights of the whole run packed
+    once (one launch), then one fused launch per block; the residual stream fp32 inside the run.
+    Returns out (x's dtype) and the saved list: the fragment images, then per block x_i, t2_i, t3_i."""
+    x = as_cl(x)
+    b, c, h, w, d = x.shape
+    nb = plan.blocks[0].branch_conv1.weight.shape[0]
+    ptab, _ = plan.tables(x.device)
+    img, per = preact_wide_pack(ptab, len(plan.blocks), c, nb, x.device, dtype=x.dtype)
+    base = img.data_ptr()
+    xs = cast(x, torch.float32)
+    saved = [img]
+    for i, blk in enumerate(plan.blocks):
+        out, t2, t3 = preact_wide_fwd(xs, base + i * per, blk, save=save, dtype=x.dtype)
+        if save:
+            saved += [xs, t2, t3]
+        xs = out
+    return cast(xs, x.dtype), saved
 
 
-def preact_wide_wgrad_run(plan, shape, run_ws, stride, gs, xs, t2s, t3s):
-    """Every block's weight-gradient partial rows of a wide run, one launch (after the data chain;
-    per-block lists: incoming gradient, input, saved t2 / t3)."""
-    b, c, h, w, d = shape
+def preact_wide_run_bwd(g, plan, saved, in_dtype):
+    """Backward of preact_wide_run_fwd: two launches per block (data path, weight-gradient partials
+    into a slice of one run workspace; the latter as one launch for the run when batched) plus one
+    fixed-order reduction launch for the whole run; the gradient stream fp32 inside the run.  Returns
+    gx of the run's input, in in_dtype."""
+    img, *flat = saved
     n = len(plan.blocks)
-    ptab, _ = plan.tables(run_ws.device)
-    arr = ctypes.c_void_p * n
-    L.call("vq3d_preact_wide_wgrad_run", L.dtype_code(t2s[0]), n, b, h, w, d, arr(*[t.data_ptr() for t in gs]),
-           arr(*[t.data_ptr() for t in xs]), arr(*[t.data_ptr() for t in t2s]), arr(*[t.data_ptr() for t in t3s]),
-           L.ptr(ptab), L.ptr(run_ws), ctypes.c_size_t(stride), L.stream())
-
-
-def preact_wide_reduce_run(plan, shape, run_ws, stride):
-    """The fixed-order gradient reductions of every block of a wide run, one launch."""
-    b, c, h, w, d = shape
-    ptab, gtab = plan.tables(run_ws.device)
-    args = (len(plan.blocks), b, h, w, d, L.ptr(run_ws), ctypes.c_size_t(stride), L.ptr(gtab), L.ptr(ptab))
+    base, per = img.data_ptr(), img.numel() // n  # the per-block image stride of preact_wide_pack
+    gs = cast(to_cl(g), torch.float32)
+    b, c, h, w, d = gs.shape
+    run_ws, wbase, stride = run_workspace(L.query("vq3d_preact_wide_workspace_bytes", b, h, w, d), n, gs.device)
+    batched = _batched_wgrad and not _concurrent
+    run = [None] * n  # batched: (g, x, t2, t3) per block for one weight launch
+    for i, (xs, t2, t3) in reversed(list(enumerate(_trios(flat, n)))):
+        if batched:
+            run[i] = (gs, xs, t2, t3)
+        gs = preact_wide_bwd(gs, xs, t2, t3, base + i * per, plan.blocks[i], block_grads(plan.blocks[i]),
+                             ws_ptr=wbase + i * stride, reduce=False, weights=not batched)
+    ptab, gtab = plan.tables(gs.device)
+    if batched:  # every block's weight-gradient partial rows, one launch after the data chain
+        gl, xl, t2l, t3l = zip(*run)
+        L.call("vq3d_preact_wide_wgrad_run", L.dtype_code(t2l[0]), n, b, h, w, d, _ptrs(gl), _ptrs(xl), _ptrs(t2l),
+               _ptrs(t3l), L.ptr(ptab), L.ptr(run_ws), ctypes.c_size_t(stride), L.stream())
+    red = (n, b, h, w, d, L.ptr(run_ws), ctypes.c_size_t(stride), L.ptr(gtab), L.ptr(ptab))
     if _concurrent:
-        _on_side(run_ws.device, lambda: L.call("vq3d_preact_wide_reduce_run", *args, L.stream()), run_ws, ptab, gtab)
+        _on_side(gs.device, lambda: L.call("vq3d_preact_wide_reduce_run", *red, L.stream()), run_ws, ptab, gtab)
     else:
-        L.call("vq3d_preact_wide_reduce_run", *args, L.stream())
+        L.call("vq3d_preact_wide_reduce_run", *red, L.stream())
+    return cast(gs, in_dtype)
+
+
+# ------------------------------------------------------------------------------------------------ stack
+def stack_supported(dtype, shape, branch):
+    b, c, h, w, d = shape
+    return (dtype in (torch.float32, torch.bfloat16, torch.float16)
+            and bool(L.query("vq3d_preact_stack_supported", b, c, branch, h, w, d)))
+
+
+def _stack_dims(t, plan):
+    b, c, h, w, d = t.shape
+    return len(plan.blocks), b, c, plan.blocks[0].branch_conv1.weight.shape[0], h, w, d
+
+
+def preact_stack_run_fwd(x, plan, save=True):
+    """A RUN of identical blocks on a tiny grid, forward in ONE launch (preact_stack.hip), the
+    residual stream fp32 inside the run.  Returns out and [the saved fp32 intermediates]."""
+    x = as_cl(x)
+    dims = _stack_dims(x, plan)
+    ptab, _ = plan.tables(x.device)
+    saved = torch.empty(L.query("vq3d_preact_stack_saved_floats", *dims), dtype=torch.float32, device=x.device)
+    out = torch.empty_like(x, memory_format=CL)
+    _timed("k_stackm_fwd", lambda: L.call("vq3d_preact_stack_fwd", L.dtype_code(x), *dims, L.ptr(x), L.ptr(ptab),
+                                          L.ptr(out), L.ptr(saved), L.stream()))
+    return out, [saved]
+
+
+def preact_stack_run_bwd(g, plan, saved, in_dtype=None):
+    """Backward of preact_stack_run_fwd, one entry point (vq3d_preact_stack_bwd_ws)."""
+    (saved,) = saved
+    g = to_cl(g)
+    dims = _stack_dims(g, plan)
+    ptab, gtab = plan.tables(g.device)
+    gx = torch.empty_like(g, memory_format=CL)
+    nws = L.query("vq3d_preact_stack_bwd_workspace_bytes", *dims)
+    ws = workspace(nws, g.device)
+    _timed("k_stackm_bwd", lambda: L.call("vq3d_preact_stack_bwd_ws", L.dtype_code(g), *dims, L.ptr(g), L.ptr(ptab),
+                                          L.ptr(gtab), L.ptr(saved), L.ptr(gx), L.ptr(ws), max(nws, 256), L.stream()))
+    return gx
 
 
 # ------------------------------------------------------------------------------------------------ misc

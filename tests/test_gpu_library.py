@@ -103,6 +103,58 @@ def test_library_step_matches_ctypes(gpu, name):
     assert not d, worst
 
 
+# (block path, in channels, out channels, mode, input shape, fused few-channel backward): bf16
+BLOCK_PATHS = [("tiny", 8, 8, "same", (1, 8, 4, 4, 4), True), ("small", 8, 8, "same", (1, 8, 8, 8, 8), True),
+               ("small", 8, 8, "same", (1, 8, 8, 8, 8), False), ("mid", 18, 18, "same", (1, 18, 8, 8, 16), True),
+               ("convs", 4, 8, "down", (1, 4, 8, 8, 8), True)]
+
+
+@pytest.mark.parametrize("path,cin,cout,mode,shape,fused_bwd", BLOCK_PATHS,
+                         ids=[f"{p[0]}{'' if p[5] else '-convs_bwd'}" for p in BLOCK_PATHS])
+def test_block_path_tag_through_both_bindings(gpu, path, cin, cout, mode, shape, fused_bwd):
+    """One PreActFixupResBlock forward + backward per block path (Fn.block_path) through the ctypes binding
+    and through vq3d::preact_block / _backward, which carry the path tag (ctx.path, ctx.fused_bwd) in the
+    operator's meta tensor: out, gx and every parameter gradient bit for bit."""
+    from vq3d import functional as Fn
+    from vq3d import layers as VL
+    from vq3d import ops
+    from vq3d.flat import FlatParams
+    cl = torch.channels_last_3d
+    torch.manual_seed(11)
+    blk = VL.PreActFixupResBlock(cin, cout, mode=mode)
+    with torch.no_grad():
+        for p in blk.parameters():
+            p.add_(0.2 * torch.randn_like(p))
+    blk = blk.to(gpu)
+    FlatParams(blk.parameters(), gpu)
+    x = torch.randn(shape, generator=torch.Generator().manual_seed(12)).bfloat16().to(gpu)
+    x = x.contiguous(memory_format=cl)
+    ops.set_small_blocks(True, fused_bwd)
+    try:
+        assert Fn.block_path(x.dtype, x.shape, blk) == path
+        assert path != "small" or ops.small_backward_fused(x) == fused_bwd
+        res = []
+        for binding in ("ctypes", "library"):
+            Fn.set_binding(binding)
+            for p in blk.parameters():
+                p.grad.zero_()
+            xa = x.clone().requires_grad_(True)
+            y = blk(xa)
+            gy = torch.randn(y.shape, generator=torch.Generator().manual_seed(13)).bfloat16().to(gpu)
+            y.backward(gy.contiguous(memory_format=cl))
+            ops.join_side()
+            torch.cuda.synchronize()
+            res.append((y.detach().clone(), xa.grad.clone(), {n: p.grad.clone() for n, p in blk.named_parameters()}))
+    finally:
+        Fn.set_binding("ctypes")
+        ops.set_small_blocks(True, True)
+    (ya, gxa, ga), (yb, gxb, gb) = res
+    assert torch.equal(ya, yb) and torch.equal(gxa, gxb)
+    assert float(gxa.float().abs().max()) > 0
+    for n in ga:
+        assert torch.equal(ga[n], gb[n]), (n, _rel(gb[n], ga[n]))
+
+
 def test_library_ops_are_the_kernels(gpu):
     """A circular 3x3x3 conv through the library binding (lb.conv: the operator below the autograd
     key + its formula), and through torch.ops.vq3d.conv3d called directly under autograd (the
