@@ -468,6 +468,38 @@ __global__ __launch_bounds__(256) void k_preact_act_bwd(int64_t n, const TG *__r
     }
     grid_sum2<256>(gsum, sa, sb, da, db, red);
 }
+// the conditioned block's glue: y = elu(x + p + a) + b; its backward gx = g elu'(x + p + a) with the a / b
+// sums (fixed order, grid_sum2).  One dtype for x, p, g, y.
+template <typename T>
+__global__ __launch_bounds__(256) void k_preact_add_act_fwd(int64_t n, const T *__restrict__ x,
+                                                           const T *__restrict__ p, const float *a, const float *b,
+                                                           T *__restrict__ y) {
+    const float av = *a, bv = *b;
+    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256)
+        st(y + i, elu(ld(x + i) + ld(p + i) + av) + bv);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_preact_add_act_bwd(int64_t n, const T *__restrict__ g,
+                                                           const T *__restrict__ x, const T *__restrict__ p,
+                                                           const float *a, T *__restrict__ gx, float *da, float *db,
+                                                           GridSum gsum) {
+    __shared__ float red[8];
+    const float av = *a;
+    float sa = 0.f, sb = 0.f;
+    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256) {
+        const float gv = ld(g + i), v = gv * elu_grad(ld(x + i) + ld(p + i) + av);
+        if (gx) st(gx + i, v);
+        sa += v;
+        sb += gv;
+    }
+    {  // both sums in one barrier pair (bit-identical to two block_sum calls)
+        float pp[2] = {sa, sb};
+        block_sums<float, 256, 2, 4>(pp, red);
+        sa = pp[0];
+        sb = pp[1];
+    }
+    grid_sum2<256>(gsum, sa, sb, da, db, red);
+}
 // 4 consecutive elements (16-byte fp32 / 8-byte 16-bit accesses)
 __device__ __forceinline__ void ld4(const float *p, float v[4]) {
     const float4 q = *reinterpret_cast<const float4 *>(p);
@@ -959,6 +991,36 @@ int vq3d_preact_act_bwd(int32_t g_dtype, int32_t x_dtype, int64_t n, const void 
     }
 #undef PAB
     return check_launch("preact_act_bwd");
+}
+
+int vq3d_preact_add_act_fwd(int32_t dtype, int64_t n, const void *x, const void *p, const float *a, const float *b,
+                            void *y, vq3d_stream_t stream) {
+    if (n <= 0) return 0;
+    if (!glue_dtype(dtype)) return fail("preact_add_act_fwd: dtype");
+    if (!x || !p || !a || !b || !y) return fail("preact_add_act_fwd: null pointer");
+    hipStream_t s = as_stream(stream);
+    if (dtype == VQ3D_F32)
+        k_preact_add_act_fwd<float><<<grid_for(n), 256, 0, s>>>(n, (const float *)x, (const float *)p, a, b, (float *)y);
+    else
+        k_preact_add_act_fwd<h16_t><<<grid_for(n), 256, 0, s>>>(n, (const h16_t *)x, (const h16_t *)p, a, b, (h16_t *)y);
+    return check_launch("preact_add_act_fwd");
+}
+
+int vq3d_preact_add_act_bwd(int32_t dtype, int64_t n, const void *g, const void *x, const void *p, const float *a,
+                            void *gx, float *da, float *db, vq3d_stream_t stream) {
+    if (n <= 0) return 0;
+    if (!glue_dtype(dtype)) return fail("preact_add_act_bwd: dtype");
+    if (!g || !x || !p || !a) return fail("preact_add_act_bwd: null pointer");
+    hipStream_t s = as_stream(stream);
+    const unsigned nb = grid_for(n);
+    const GridSum gs = grid_sum_for(s, nb, da || db);
+    if (dtype == VQ3D_F32)
+        k_preact_add_act_bwd<float><<<nb, 256, 0, s>>>(n, (const float *)g, (const float *)x, (const float *)p, a,
+                                                      (float *)gx, da, db, gs);
+    else
+        k_preact_add_act_bwd<h16_t><<<nb, 256, 0, s>>>(n, (const h16_t *)g, (const h16_t *)x, (const h16_t *)p, a,
+                                                      (h16_t *)gx, da, db, gs);
+    return check_launch("preact_add_act_bwd");
 }
 
 int vq3d_scale_bias_res_fwd(int32_t o_dtype, int64_t n, const void *o, const float *scale, const float *bias,

@@ -10,7 +10,7 @@ from .metrics import SSIM3DSlices, SliceMetrics, nmse, psnr, slice_metrics  # no
 __all__ = ["VQVAE", "default_args", "Encoder2", "Decoder", "PreActFixupResBlock", "FixupResBlock",
            "EvonormResBlock", "Quantizer", "ResizeConv3D", "EvoNorm3DS0", "DownBlock", "UpBlock",
            "PreQuantizationConditioning", "Conv3d", "slice_metrics", "SliceMetrics", "SSIM3DSlices", "nmse", "psnr",
-           "sample_codes"]
+           "sample_codes", "PixelCNN", "cond_embed_reference"]
 
 
 def __getattr__(name):
@@ -19,4 +19,10 @@ def __getattr__(name):
     if name == "sample_codes":
         from .sample import sample_codes
         return sample_codes
+    if name == "PixelCNN":  # the priors load on first use (vq3d.pixelcnn pulls in the PixelSNAIL layers)
+        from .pixelcnn import PixelCNN
+        return PixelCNN
+    if name == "cond_embed_reference":  # (vq3d.cond_embed is the module; its function vq3d.cond_embed.cond_embed)
+        from .cond_embed import cond_embed_reference
+        return cond_embed_reference
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -147,6 +147,11 @@ _SIGS = {
                                        c_int, P, P]),
     "vq3d_prior_head_loss_fwd": (c_int, [c_int, c_i64, c_int, c_int, P, c_i64, P, c_i64] + [P] * 7 + [P]),
     "vq3d_prior_head_loss_bwd": (c_int, [c_int, c_i64, c_int, c_int, P, c_i64, P, c_i64] + [P] * 7 + [c_i64, P]),
+    "vq3d_cond_embed_fwd": (c_int, [c_int] * 11 + [P] * 7),
+    "vq3d_cond_embed_bwd_workspace_bytes": (c_size, [c_int] * 5),
+    "vq3d_cond_embed_bwd": (c_int, [c_int] * 10 + [P] * 7 + [c_size, P]),
+    "vq3d_preact_add_act_fwd": (c_int, [c_int, c_i64, P, P, P, P, P, P]),
+    "vq3d_preact_add_act_bwd": (c_int, [c_int, c_i64, P, P, P, P, P, P, P, P]),
     "vq3d_last_error": (ctypes.c_char_p, []),
     "vq3d_version": (ctypes.c_char_p, []),
 }

@@ -18,6 +18,7 @@ vqvae/layers.py:134-171 nn.Conv3d, :685-728 the Quantizer, model.py:115-163 the 
                                               no autograd: a metric, not a loss)
     vq3d::prior_sample_step                   the prior sampler's head + draw at one raster position
                                               (pixel_model/pixelsnail.py:256-269; in place, no autograd)
+    vq3d::cond_embed / _backward              the conditioned PixelCNN's condition embedding (vq3d.cond_embed)
     vq3d::prior_head_loss / _backward         the prior's output head fused with the cross-entropy and
                                               the argmax (pixel_model/pixelsnail.py:78-82, 112-161)
 
@@ -603,6 +604,52 @@ def _hl_bwd(ctx, grads):
 _register("prior_head_loss", _hl_bwd, _hl_setup, (0, 1, 2))
 
 
+@torch.library.custom_op("vq3d::cond_embed", mutates_args=())
+def cond_embed(codes: Tensor, table: Tensor, bias: Tensor, dims: List[int], d_out: int, lam: Optional[Tensor],
+               index: Optional[Tensor]) -> Tensor:
+    """e (b, M, d_out, H, W) channels-last in the (Kc, M) table's dtype: the conditioned PixelCNN's condition
+    embedding of int64 (b, cd, ch, cw) codes on the (D, H, W) grid `dims` (vq3d.cond_embed.cond_embed is the
+    public form)"""
+    from . import cond_embed as C
+    return C.cond_embed_fwd_kernel(codes, table, bias, tuple(dims), d_out, lam, index)
+
+
+@torch.library.custom_op("vq3d::cond_embed_backward", mutates_args=("dwe", "dbe"))
+def cond_embed_backward(g: Tensor, codes: Tensor, kc: int, lam: Optional[Tensor], index: Optional[Tensor],
+                        dwe: Tensor, dbe: Tensor) -> None:
+    """dwe (M, Kc) and dbe (M,) fp32 += the gradients of the weight and the bias from g, the gradient of the
+    full-grid e"""
+    from . import cond_embed as C
+    C.cond_embed_bwd_kernel(g, codes, kc, lam, index, dwe, dbe)
+
+
+def _ce_setup(ctx, inputs, output):
+    codes, table, bias, dims, d_out, lam, index = inputs
+    ctx.save_for_backward(*[t for t in (codes, lam, index) if t is not None])
+    ctx.mix = lam is not None and index is not None
+    ctx.table = (tuple(table.shape), table.dtype)
+    ctx.full = d_out == dims[0]
+
+
+def _ce_bwd(ctx, grads):
+    """a direct torch.ops.vq3d.cond_embed call under autograd: the gradients of the (Kc, M) table and of the
+    bias come back through autograd (the model's path, vq3d.cond_embed.CondEmbedFn, adds the parameters'
+    into their gradient buffers instead)"""
+    if not ctx.full:
+        raise RuntimeError("cond_embed: the backward takes the gradient of the full grid (d_out == D)")
+    saved = list(ctx.saved_tensors)
+    codes = saved[0]
+    lam, index = (saved[1], saved[2]) if ctx.mix else (None, None)
+    (kc, m), dt = ctx.table
+    dwe = ops.zero_(torch.empty((m, kc), dtype=torch.float32, device=codes.device))
+    dbe = ops.zero_(torch.empty((m,), dtype=torch.float32, device=codes.device))
+    torch.ops.vq3d.cond_embed_backward(grads.contiguous(memory_format=_CL), codes, kc, lam, index, dwe, dbe)
+    return None, dwe.t().to(dt), dbe, None, None, None, None
+
+
+_register("cond_embed", _ce_bwd, _ce_setup, (1, 2))
+
+
 def upsample(x):
     return _call("upsample2x", (x,), (x,))
 
@@ -739,6 +786,16 @@ def _prior_head_loss_backward_fake(gloss, hidden, weight, bias, target_a, target
     return torch.empty((hidden.shape[0], weight.shape[0]), dtype=hidden.dtype, device=hidden.device)
 
 
+@torch.library.register_fake("vq3d::cond_embed")
+def _cond_embed_fake(codes, table, bias, dims, d_out, lam, index):
+    return _act_like(table, (codes.shape[0], table.shape[1], d_out, dims[1], dims[2]))
+
+
+@torch.library.register_fake("vq3d::cond_embed_backward")
+def _cond_embed_backward_fake(g, codes, kc, lam, index, dwe, dbe):
+    return None
+
+
 for _n in ("conv3d_backward", "preact_block_backward", "preact_run_backward", "parse_input_backward",
            "recon_loss_backward"):
     torch.library.register_fake(f"vq3d::{_n}")(_eager_only(_n))
@@ -747,4 +804,4 @@ for _n in ("conv3d_backward", "preact_block_backward", "preact_run_backward", "p
 OPS = ("conv3d", "conv3d_backward", "preact_block", "preact_block_backward", "preact_run", "preact_run_backward",
        "vq_init", "vq_nearest", "vq_nearest_backward", "vq_ema", "parse_input", "parse_input_backward", "upsample2x",
        "upsample2x_backward", "recon_loss", "recon_loss_backward", "slice_metrics", "prior_sample_step",
-       "prior_head_loss", "prior_head_loss_backward")
+       "prior_head_loss", "prior_head_loss_backward", "cond_embed", "cond_embed_backward")

@@ -303,6 +303,46 @@ class ScaleBiasResFn(torch.autograd.Function):
                 (g if ctx.needs_input_grad[3] else None))
 
 
+class PreActAddFn(torch.autograd.Function):
+    """elu(x + p + a) + b, the conditioned block's pre-activation of branch_conv3's input (layers.py:458-461:
+    the condition projection p added to branch_conv2's output x, both in the conv operand format): one
+    launch instead of an add and PreActFn; backward one launch, gx = g elu'(x + p + a) written once and
+    returned for x and p alike, the a / b sums as PreActFn."""
+
+    @staticmethod
+    def forward(ctx, x, p, a, b):
+        x, p = cl(x), cl(p)
+        if p.dtype != x.dtype or p.shape != x.shape:
+            raise ValueError(f"the condition {tuple(p.shape)} {p.dtype} does not fit the stream {tuple(x.shape)} {x.dtype}")
+        y = torch.empty_like(x, memory_format=CL)
+        L.call("vq3d_preact_add_act_fwd", L.dtype_code(x), x.numel(), L.ptr(x), L.ptr(p), L.ptr(a), L.ptr(b), L.ptr(y),
+               L.stream())
+        ctx.save_for_backward(x, p)
+        ctx.prm = (a, b)
+        ctx.lst = _lane_ctx()
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, p = ctx.saved_tensors
+        a, b = ctx.prm
+        g = cl(g)
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        gx = torch.empty_like(x, memory_format=CL) if want else None
+        da, db = _sgrad(ctx.lst, a), _sgrad(ctx.lst, b)
+        L.call("vq3d_preact_add_act_bwd", L.dtype_code(x), x.numel(), L.ptr(g), L.ptr(x), L.ptr(p), L.ptr(a),
+               None if gx is None else L.ptr(gx), L.ptr(da), L.ptr(db), L.stream())
+        return (gx if ctx.needs_input_grad[0] else None, gx if ctx.needs_input_grad[1] else None,
+                None if _direct(a) else da, None if _direct(b) else db)
+
+
+def _preact_add(x, p, pro):
+    """the conv operand of elu(x + p + a) + b"""
+    if _fused_glue():
+        return PreActAddFn.apply(x, p, pro[0], pro[1])
+    return _operand(F.elu(x + p + pro[0]) + pro[1])
+
+
 def _preact(x, pro):
     """the conv operand of elu(x + a) + b"""
     if _fused_glue():
@@ -595,6 +635,17 @@ class ExpandRFConv(nn.Module):
         return torch.stack(self.run(to_list(stack)))
 
 
+def crop_condition(p, dims):
+    """the first (d, h, w) = dims of a full-grid condition projection (layers.py:452): a crop, never an
+    interpolation to the smaller grid"""
+    d, h, w = (int(v) for v in dims)
+    if tuple(p.shape[2:]) == (d, h, w):
+        return cl(p)
+    if d > p.shape[2] or h > p.shape[3] or w > p.shape[4]:
+        raise ValueError(f"a {(d, h, w)} grid is no crop of the condition's {tuple(p.shape[2:])}")
+    return cl(p[:, :, :d, :h, :w])
+
+
 def _dropout3d(stack, mod):
     if mod is None or not mod.training or mod.p == 0:
         return stack
@@ -636,10 +687,13 @@ class PreActFixupCausalResBlock(nn.Module):
         self.activation = activation()
         self.dropout = nn.Dropout3d(dropout_prob) if dropout_prob > 0 else None
 
-    def run(self, stack, aux=None):
-        """each stream on its lane; the streams meet in expand_rf"""
+    def run(self, stack, aux=None, cond=None):
+        """each stream on its lane; the streams meet in expand_rf.  cond: the condition projection
+        self.condition(e) already cropped to the streams' grid, made on lane 0; it is added to all three
+        streams in front of branch_conv3's pre-activation (layers.py:444-461)"""
         out = self.branch_conv1.run(stack, pro=(self.bias1a, self.bias1b))
         out = self.expand_rf.run(out)
+        conds = None if cond is None else [cond, _take(1, 0, cond), _take(2, 0, cond)]
         res = []
         for i in range(3):
             with _lane(i):
@@ -649,7 +703,10 @@ class PreActFixupCausalResBlock(nn.Module):
                     o = cl(o + self.aux.run_one(i, cl(F.elu(aux[i]))))
                 o = self.branch_conv2.run_one(i, o, pro=(self.bias2a, self.bias2b))
                 o = _dropout3d([o], self.dropout)[0]
-                o = self.branch_conv3.run_one(i, o, pro=(self.bias3a, self.bias3b))
+                if conds is None:
+                    o = self.branch_conv3.run_one(i, o, pro=(self.bias3a, self.bias3b))
+                else:
+                    o = self.branch_conv3.run_one(i, _preact_add(o, conds[i], (self.bias3a, self.bias3b)))
                 s = stack[i] if self.skip_conv is None else self.skip_conv.run_one(i, stack[i])
                 # o * scale + bias4 + skip: fp32 (the 1-element fp32 parameters promote, as in the reference)
                 if _fused_glue():
@@ -658,10 +715,19 @@ class PreActFixupCausalResBlock(nn.Module):
                     res.append(cl(o * self.scale + self.bias4 + s))
         return res
 
+    def project_condition(self, condition, dims):
+        """self.condition(condition) cropped to the (d, h, w) grid `dims` (layers.py:450-452)"""
+        assert self.condition is not None, "Condition projection matrix not initialised!"
+        return crop_condition(pointwise(_operand(condition), self.condition.weight, self.condition.bias), dims)
+
     def forward(self, stack, aux=None, condition=None, condition_cache=None):
-        if condition is not None or condition_cache is not None:
-            raise NotImplementedError("conditioning (use_conditioning) is not implemented")
-        return torch.stack(self.run(to_list(stack), None if aux is None else to_list(aux)))
+        stack = to_list(stack)
+        cond = None
+        if condition_cache is not None:  # deliberately preferred over computing the projection again
+            cond = crop_condition(condition_cache.popleft(), stack[0].shape[2:])
+        elif condition is not None:
+            cond = self.project_condition(condition, stack[0].shape[2:])
+        return torch.stack(self.run(stack, None if aux is None else to_list(aux), cond))
 
     @torch.no_grad()
     def initialize_weights(self, num_layers):
@@ -830,6 +896,42 @@ def background_list(b, dims, dtype, device, full_dims=None):
     return [g, g, g]
 
 
+def begin_forward(model):
+    """the per-forward state both priors (PixelSNAIL, PixelCNN) set before their first conv: the conv
+    operand dtype, and the GEMM weights of this forward -- one cast of the flat parameter buffer (if
+    there is one)"""
+    _compute[0] = model.compute_dtype
+    _shadow[0] = None
+    if model.compute_dtype != torch.float32:
+        from .flat import flat_of
+        fl = flat_of(model.parse_input.weight)
+        if fl is not None:
+            fl.refresh_shadow(model.compute_dtype)
+            _shadow[0] = (fl, model.compute_dtype)
+
+
+@contextlib.contextmanager
+def forward_lanes(model, x):
+    """the lanes of one forward of `model` whose parse_input output is x: the three streams and the
+    _LaneGrads of the shared one-element parameters while the body runs (16-bit GPU runs with lanes on),
+    else nothing"""
+    lanes = None
+    if _lanes_on[0] and model.compute_dtype != torch.float32 and x.is_cuda:
+        # (the lane streams exist before any capture: created on the first eager forward)
+        aux = [ops.aux_stream(x.device, "psnail_lane1"), ops.aux_stream(x.device, "psnail_lane2")]
+        if _lanes_on[0] is True or torch.cuda.is_current_stream_capturing():
+            lanes = [torch.cuda.current_stream()] + aux
+    _LANES[0] = lanes
+    if lanes is not None:
+        shared = [p for p in model.parameters() if p.numel() == 1 and p.requires_grad]
+        _LSTATE[0] = _LaneGrads(shared, lanes, x.device)
+    try:
+        yield
+    finally:
+        _LANES[0] = None
+        _LSTATE[0] = None
+
+
 class PixelSNAIL(nn.Module):
     """pixel_model/pixelsnail.py:27-320 (module tree, argument parsing, init and loss of the
     reference; mixup as train_helpers.py:20-63.  Conditioning is not implemented: the published prior
@@ -909,16 +1011,8 @@ class PixelSNAIL(nn.Module):
         are the matching crop of the full-size background."""
         b = onehot.shape[0]
         dims = tuple(onehot.shape[2:])
-        _compute[0] = self.compute_dtype
         x = cl(onehot.to(self.compute_dtype))
-        # the GEMM weights of this forward: one cast of the flat parameter buffer (if there is one)
-        _shadow[0] = None
-        if self.compute_dtype != torch.float32:
-            from .flat import flat_of
-            fl = flat_of(self.parse_input.weight)
-            if fl is not None:
-                fl.refresh_shadow(self.compute_dtype)
-                _shadow[0] = (fl, self.compute_dtype)
+        begin_forward(self)
         x = cl(pointwise(x, self.parse_input.weight, self.parse_input.bias))
         bg = background_list(b, dims, self.compute_dtype, x.device, full_dims)
         if self.compute_dtype != torch.float32:
@@ -927,25 +1021,12 @@ class PixelSNAIL(nn.Module):
             # (PointwiseFn pads the weights to match; the zero channels add nothing)
             bgp = cl(F.pad(bg[0], (0, 0, 0, 0, 0, 0, 0, (-bg[0].shape[1]) % 8)))
             bg = [bgp] * len(bg)
-        lanes = None
-        if _lanes_on[0] and self.compute_dtype != torch.float32 and x.is_cuda:
-            # (the lane streams exist before any capture: created on the first eager forward)
-            aux = [ops.aux_stream(x.device, "psnail_lane1"), ops.aux_stream(x.device, "psnail_lane2")]
-            if _lanes_on[0] is True or torch.cuda.is_current_stream_capturing():
-                lanes = [torch.cuda.current_stream()] + aux
-        _LANES[0] = lanes
-        if lanes is not None:
-            shared = [p for p in self.parameters() if p.numel() == 1 and p.requires_grad]
-            _LSTATE[0] = _LaneGrads(shared, lanes, x.device)
-        try:
+        with forward_lanes(self, x):
             xs = [x] + [_take(i, 0, x, bg[0])[0] for i in (1, 2)]
             stack = self.to_causal.run(xs)
             for layer in self.layers:
                 stack = layer.run(stack, bg)
             stack = [stack[0]] + [_take(0, i, stack[i]) for i in (1, 2)]
-        finally:
-            _LANES[0] = None
-            _LSTATE[0] = None
         return _operand(stack[0] + stack[1] + stack[2])
 
     def forward(self, data, background=None, attn_mask=None, condition=None, condition_cache=None):

@@ -1,8 +1,14 @@
-"""Sampling codes from a trained PixelSNAIL prior, the counterpart of the reference's
-`PixelSNAIL.sample` (pixel_model/pixelsnail.py:219-272) and pixel_model/sample_embeddings.py.
+"""Sampling codes from a trained PixelSNAIL or PixelCNN prior, the counterpart of the reference's
+`PixelSNAIL.sample` (pixel_model/pixelsnail.py:219-272), `PixelCNN.sample` (pixelcnn.py:213-287) and
+pixel_model/sample_embeddings.py.
 
     python -m vq3d.sample PRIOR_CKPT --size d h w --num-samples N [--batch-size B] [--temperature T]
         [--seed S] --out DIR [--vqvae-ckpt CKPT --levels-from DIR... --nrrd DIR]
+        [--use-model pixelsnail|pixelcnn] [--condition-from DIR [--condition-level J]]
+
+A conditioned PixelCNN (the lower levels of a hierarchy, generated top-down) takes the codes of the level
+above from --condition-from; its layers' condition projections are computed once per batch on the full grid
+and cropped for every prefix.
 
 The reference fills a (b, K, d, h, w) tensor position by position in raster order (last axis
 fastest), runs its whole forward on the crop of everything visited so far and draws
@@ -182,7 +188,7 @@ def _seed_bits(seed):
 
 @torch.no_grad()
 def sample_codes(model, size, batch_size=1, temperature=1.0, seed=0, sample_base=0, return_logits=False,
-                 graphs=False, hidden_fn=None):
+                 graphs=False, hidden_fn=None, condition=None):
     """Draw `batch_size` code volumes of `size` = (d, h, w) from the prior `model` (in eval mode), in
     raster order: int64 (b, d, h, w) codes on the model's device; with return_logits also the fp32
     (b, K, d, h, w) logit rows each draw actually used.
@@ -193,7 +199,12 @@ def sample_codes(model, size, batch_size=1, temperature=1.0, seed=0, sample_base
     Eager: one prefix forward and one kernel launch per position.  graphs=True: one captured HIP graph
     per slab count (prefix forward, kernel, pos += 1 on a single stream, lanes off), replayed h w times.
     No host synchronisation inside the loop.  hidden_fn(prefix_onehot, full_dims) replaces
-    `model.hidden` (tests; CPU models, whose network has no CPU path)."""
+    `model.hidden` (tests; CPU models, whose network has no CPU path).
+
+    condition: int64 (b, cd, ch, cw) codes of the level above, for a conditioned prior (vq3d.pixelcnn):
+    `model.condition_cache` -- every layer's full-grid condition projection -- is computed once and
+    passed to `hidden` for every prefix, which crops it; an injected hidden_fn is called as
+    hidden_fn(prefix_onehot, full_dims, condition=condition) instead."""
     if model.training:
         raise RuntimeError("sample_codes needs model.eval(): dropout would change the conditional distributions")
     d, h, w = (int(v) for v in size)
@@ -201,8 +212,23 @@ def sample_codes(model, size, batch_size=1, temperature=1.0, seed=0, sample_base
         raise ValueError(f"bad size {tuple(size)} or batch size {batch_size}")
     weight, bias = model.parse_output.weight.detach(), model.parse_output.bias.detach()
     dev, k = weight.device, weight.shape[0]
-    hidden = model.hidden if hidden_fn is None else hidden_fn
     b, hw, npos, dims = int(batch_size), h * w, d * h * w, (d, h, w)
+    if condition is None:
+        if getattr(model, "condition_dim", 0):
+            raise ValueError("this prior is conditioned: pass `condition`, the codes of the level above")
+        hidden = model.hidden if hidden_fn is None else hidden_fn
+    else:
+        if (not torch.is_tensor(condition) or condition.dtype != torch.int64 or condition.dim() != 4
+                or condition.shape[0] != b):
+            raise ValueError(f"condition must be an int64 ({b}, cd, ch, cw) tensor")
+        if hidden_fn is not None:
+            def hidden(prefix, full_dims):
+                return hidden_fn(prefix, full_dims, condition=condition)
+        else:
+            cache = model.condition_cache(condition.to(dev), dims)
+
+            def hidden(prefix, full_dims):
+                return model.hidden(prefix, full_dims, condition_cache=cache)
     x = torch.zeros((b, k, d, h, w), dtype=model.compute_dtype, device=dev).contiguous(memory_format=CL)
     codes = torch.zeros((b, npos), dtype=torch.int64, device=dev)
     pos = torch.zeros((), dtype=torch.int64, device=dev)
@@ -255,8 +281,15 @@ def _capture(step, d, pos):
 
 # ------------------------------------------------------------------ command line
 def build_parser():
-    parser = ArgumentParser(description="sample code volumes from a PixelSNAIL prior checkpoint")
+    parser = ArgumentParser(description="sample code volumes from a PixelSNAIL or PixelCNN prior checkpoint")
     parser.add_argument("prior_ckpt", type=Path)
+    parser.add_argument("--use-model", choices=("pixelsnail", "pixelcnn"), default="pixelsnail",
+                        help="the model class of the checkpoint")
+    parser.add_argument("--condition-from", type=Path, default=None,
+                        help="code directory holding the level above (a conditioned PixelCNN's condition); sample i "
+                             "takes row i (modulo its length)")
+    parser.add_argument("--condition-level", type=int, default=0,
+                        help="which level of --condition-from is the condition")
     parser.add_argument("--size", type=int, nargs=3, required=True, metavar=("D", "H", "W"),
                         help="the code grid, in the axis order of the codes the prior was trained on")
     parser.add_argument("--num-samples", type=int, required=True)
@@ -314,9 +347,20 @@ def main(args):
         raise ValueError("--vqvae-ckpt and --nrrd go together")
     from .checkpoint import load_from_checkpoint
     from .extract import CodeStore
-    from .pixelsnail import PixelSNAIL
+    if getattr(args, "use_model", "pixelsnail") == "pixelcnn":
+        from .pixelcnn import PixelCNN as Model
+    else:
+        from .pixelsnail import PixelSNAIL as Model
     dev = torch.device("cuda", torch.cuda.current_device())
-    model = load_from_checkpoint(PixelSNAIL, str(args.prior_ckpt)).to(dev)
+    model = load_from_checkpoint(Model, str(args.prior_ckpt)).to(dev)
+    conditioned = bool(getattr(model, "condition_dim", 0))
+    cond_dir = getattr(args, "condition_from", None)
+    if conditioned != (cond_dir is not None):
+        raise ValueError("--condition-from is required exactly when the prior is conditioned "
+                         f"(this checkpoint's condition_dim is {getattr(model, 'condition_dim', 0)})")
+    cond_rows = None
+    if conditioned:
+        cond_rows = np.load(os.path.join(str(cond_dir), f"level{args.condition_level}.npy"), mmap_mode="r")
     model.compute_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
     model.eval()
     n, size = args.num_samples, tuple(args.size)
@@ -324,7 +368,12 @@ def main(args):
     with CodeStore(str(args.out), [model.input_dim], n) as store:
         for base in range(0, n, args.batch_size):
             bs = min(args.batch_size, n - base)
-            c = sample_codes(model, size, bs, args.temperature, args.seed, base, graphs=args.graphs).cpu().numpy()
+            cond = None
+            if cond_rows is not None:
+                rows = np.stack([np.array(cond_rows[(base + i) % cond_rows.shape[0]]) for i in range(bs)])
+                cond = torch.from_numpy(rows.reshape((bs,) + rows.shape[-3:]).astype(np.int64)).to(dev)
+            c = sample_codes(model, size, bs, args.temperature, args.seed, base, graphs=args.graphs,
+                             condition=cond).cpu().numpy()
             for i in range(bs):
                 sampled[base + i, 0] = c[i]
                 store.put(base + i, [sampled[base + i]])

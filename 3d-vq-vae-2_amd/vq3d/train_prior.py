@@ -1,4 +1,5 @@
-"""Training entry for the PixelSNAIL priors over extracted codes, mirroring the reference's
+"""Training entry for the PixelSNAIL priors over extracted codes (vq3d.train_pixelcnn drives the same
+datamodule, metrics, validation, checkpointing and fit loop for the PixelCNN priors), mirroring the reference's
 pixel_model/train.py + utils/load_lmdb_dataset.py:12-50 + PixelSNAIL.shared_step on the vq3d path:
 
     python -m vq3d.train_prior CODES LEVEL --use-model pixelsnail --metric cross_entropy
@@ -57,8 +58,9 @@ def build_parser(argv=None):
     parser.add_argument("--use-model", type=str, choices=["pixelcnn", "pixelsnail"], default="pixelcnn")
     use_model = parser.parse_known_args(argv)[0].use_model
     if use_model == "pixelcnn":
-        raise NotImplementedError("--use-model pixelcnn: the PixelCNN prior is not implemented (DESIGN.md §8); "
-                                  "pass --use-model pixelsnail")
+        raise NotImplementedError("--use-model pixelcnn: this entry trains PixelSNAIL priors only (DESIGN.md §8); the "
+                                  "PixelCNN prior has its own, python -m vq3d.train_pixelcnn -- or pass "
+                                  "--use-model pixelsnail")
     parser = PixelSNAIL.add_model_specific_args(parser)
     parser = T.add_trainer_args(parser)
     parser.add_argument("dataset_path", type=Path)
@@ -133,6 +135,18 @@ def _codes(batch, dev):
     return torch.as_tensor(batch[0]).squeeze(1).to(dev, non_blocking=True).long()
 
 
+def _condition(batch, dev, model):
+    """the batch's second tensor -- the level above -- as int64 (b, cd, ch, cw) condition codes when the
+    model is conditioned (pixelcnn.py:106-113), else None"""
+    if len(batch) == 1 or not getattr(model, "use_conditioning", False):
+        return None
+    return torch.as_tensor(batch[1]).squeeze(1).to(dev, non_blocking=True).long()
+
+
+def _cond_kw(cond):
+    return {} if cond is None else {"condition": cond}
+
+
 def validate(model, loader, dev):
     """The mean of every VAL_KEYS value over the validation batches of all ranks (as train.validate):
     returns val_loss_mean (None without batches), all seven in model.val_metrics."""
@@ -141,7 +155,8 @@ def validate(model, loader, dev):
     with torch.no_grad():
         for batch in loader:
             codes = _codes(batch, dev)
-            rows, pred = model.loss_rows(onehot_codes(codes, model.input_dim), codes)
+            rows, pred = model.loss_rows(onehot_codes(codes, model.input_dim), codes,
+                                         **_cond_kw(_condition(batch, dev, model)))
             m = loss_metrics(rows, "val")
             m["val_accuracy"] = (pred == codes).double().mean()
             tot += torch.stack([m[k] for k in VAL_KEYS])
@@ -157,20 +172,23 @@ def validate(model, loader, dev):
 
 
 # ------------------------------------------------------------------ training
-def main(args: Namespace, datamodule=None):
-    """pixel_model/train.py:55-77."""
+def main(args: Namespace, datamodule=None, model_cls=PixelSNAIL):
+    """pixel_model/train.py:55-77.  model_cls: PixelSNAIL, or vq3d.pixelcnn.PixelCNN (vq3d.train_pixelcnn),
+    whose conditioned form takes the batch's second tensor as its condition."""
     rank, world, _, dev = parallel.init_from_env()
     if dev.type != "cuda":
-        raise RuntimeError("vq3d.train_prior runs the HIP path: a GPU is required")
-    if getattr(args, "use_conditioning", False):
-        raise NotImplementedError("conditioning (use_conditioning) is not implemented")
+        raise RuntimeError("the priors train on the HIP path: a GPU is required")
+    if model_cls is PixelSNAIL and getattr(args, "use_conditioning", False):
+        raise NotImplementedError("conditioning (use_conditioning) is not implemented for PixelSNAIL")
     T.seed_everything(42)
     if datamodule is None:
         datamodule = CodesDataModule(path=args.dataset_path, embedding_id=args.level, batch_size=args.batch_size,
                                      num_workers=5)
     datamodule.setup()
     args.num_embeddings = [int(k) for k in datamodule.num_embeddings]
-    model = PixelSNAIL(args, compute_dtype=getattr(args, "compute_dtype", "bf16")).to(dev)
+    if getattr(args, "use_conditioning", False) and not args.num_embeddings[1]:
+        raise ValueError(f"level {args.level} is the top of its store: there is no level above to condition on")
+    model = model_cls(args, compute_dtype=getattr(args, "compute_dtype", "bf16")).to(dev)
     model.train()
     model.flat = FlatParams(model.parameters(), dev)  # what parallel.GradientAllReduce averages
     opt = FusedAdam(model.parameters(), model.flat, lr=model.lr, amsgrad=True)
@@ -209,9 +227,9 @@ def _fit(args, model, opt, reducer, ckpt, datamodule, rank, world, dev, epoch0, 
     index_t = torch.arange(bsz, dtype=torch.int64, device=dev)
     last = {}
 
-    def train_step(codes):
+    def train_step(codes, cond=None):  # cond: the captured step's second static input
         opt.zero_grad()
-        rows, _ = model.loss_rows(onehot_codes(codes, k), codes, (lam_t, index_t) if mixup else None)
+        rows, _ = model.loss_rows(onehot_codes(codes, k), codes, (lam_t, index_t) if mixup else None, **_cond_kw(cond))
         loss = rows.mean()
         scaler.scale(loss).backward()
         reducer()
@@ -230,12 +248,12 @@ def _fit(args, model, opt, reducer, ckpt, datamodule, rank, world, dev, epoch0, 
         if sampler is not None:
             sampler.set_epoch(epoch)
         for i, batch in enumerate(loader):
-            codes = _codes(batch, dev)
+            codes, cond = _codes(batch, dev), _condition(batch, dev, model)
             if mixup:
                 lam, index = mixup_draw(bsz, model.mixup_alpha)
                 lam_t.copy_(torch.tensor(lam, dtype=torch.float32), non_blocking=True)
                 index_t.copy_(index.to(torch.int64), non_blocking=True)
-            runner(codes)
+            runner(*((codes,) if cond is None else (codes, cond)))
             step += 1
             if step % args.log_every_n_steps == 0 or step == 1:
                 log = {name: float(v) for name, v in loss_metrics(last["rows"], "train").items()}
@@ -258,16 +276,16 @@ def _fit(args, model, opt, reducer, ckpt, datamodule, rank, world, dev, epoch0, 
     return model, opt, history, ckpt
 
 
-def cli(argv=None, datamodule=None):
+def cli(argv=None, datamodule=None, parse=None, module="vq3d.train_prior", model_cls=PixelSNAIL):
     """The command: the ranks' exit code when it started them (--gpus > 1), else main's
     (model, optimizer, log history, checkpointer) of the run in this process."""
     import sys
     argv = sys.argv[1:] if argv is None else argv
-    args = parse_arguments(argv)
-    rc = T.launch_ranks(args, argv, module="vq3d.train_prior")
+    args = (parse or parse_arguments)(argv)
+    rc = T.launch_ranks(args, argv, module=module)
     if rc is not None:
         return rc
-    return main(args, datamodule)
+    return main(args, datamodule, model_cls)
 
 
 if __name__ == "__main__":

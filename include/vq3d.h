@@ -645,6 +645,44 @@ int vq3d_prior_head_loss_bwd(int32_t dtype, int64_t nrows, int32_t c, int32_t k,
                              const int64_t *target_b, const float *lam, const float *lse, const float *gloss,
                              void *dlogits, int64_t ldg, vq3d_stream_t stream);
 
+/* --- conditioned PixelCNN prior: the condition embedding (pixel_model/pixelcnn.py:113-128, :294, :310:
+ * embed_condition of the trilinearly interpolated one-hot of the upper level's codes, with mixup's blend of
+ * the interpolated one-hot, train_helpers.py:48-53) as a blend of rows of the embedding table, without the
+ * one-hot or its interpolation in memory.  codes: int64 [b][cd][ch][cw]; the lower grid is (D, H, W).  Per
+ * axis n_in -> n_out (ATen's align_corners = False rule, fp32): s = float(n_in) / float(n_out),
+ * src = max(s * (o + 0.5) - 0.5, 0), i0 = min(floor(src), n_in - 1), i1 = i0 + (i0 < n_in - 1),
+ * t1 = src - i0, t0 = 1 - t1.  For voxel v = (z, y, x) of sample B:
+ *   e0[B][v][:] = sum over the 8 corners j of tz * ty * tx * table[codes[B][corner_j(v)]][:]
+ *   e[B][v][:]  = bias + lam * e0[B][v][:] + (1 - lam) * e0[index[B]][v][:]      (lam or index NULL: bias + e0)
+ * fp32 weights and accumulation, one rounding to dtype.  A code outside [0, kc) contributes nothing: codes
+ * are compared, never used as addresses; an index value outside [0, b) stands for the sample itself (no mixing).
+ * table: [kc][m] rows in dtype (the transposed embed_condition weight), 16-byte aligned; bias fp32 [m]; lam
+ * (fp32) and index (int64 [b]) device pointers, read when the kernel runs and never written.  e:
+ * [b][d_out][H][W][m] in dtype, the first d_out <= D slabs of the full grid, 16-byte aligned.
+ * dtype F32 / BF16 / F16; m % 8 == 0, m <= 1024; 8 <= kc <= 1024; every axis of both grids <= 2^20.
+ * The backward takes g = de/d(e) of the FULL grid, [b][D][H][W][m] in dtype, and adds in fp32
+ *   dwe[c][k] += sum of the weights' terms of code k times g[..][c]   (the parameter's own [m][kc] layout)
+ *   dbe[c]    += sum g[..][c]
+ * in two launches: the adjoint interpolation in gather form (every coarse voxel of source sample B' sums, in
+ * index order, the fine voxels that name it as a corner, destination B' weighted lam and every B with
+ * index[B] == B' weighted 1 - lam) into the fp32 workspace [b][cd ch cw][m], then one workgroup per code
+ * summing its rows in order.  Deterministic: no atomics, fixed summation order.  dwe or dbe may be NULL. */
+int vq3d_cond_embed_fwd(int32_t dtype, int32_t b, int32_t cd, int32_t ch, int32_t cw, int32_t d, int32_t h,
+                        int32_t w, int32_t d_out, int32_t m, int32_t kc, const int64_t *codes, const void *table,
+                        const float *bias, const float *lam, const int64_t *index, void *e, vq3d_stream_t stream);
+size_t vq3d_cond_embed_bwd_workspace_bytes(int32_t b, int32_t cd, int32_t ch, int32_t cw, int32_t m);
+int vq3d_cond_embed_bwd(int32_t dtype, int32_t b, int32_t cd, int32_t ch, int32_t cw, int32_t d, int32_t h,
+                        int32_t w, int32_t m, int32_t kc, const int64_t *codes, const void *g, const float *lam,
+                        const int64_t *index, float *dwe, float *dbe, void *workspace, size_t ws_bytes,
+                        vq3d_stream_t stream);
+/* the conditioned block's pre-activation of branch_conv3's input (layers.py:458-461):
+ * y = elu(x + p + *a) + *b, with x, p, y n elements of one dtype; its backward gx = g * elu'(x + p + a)
+ * (the gradient of x and of p alike; may be NULL), *da += sum gx, *db += sum g (fixed order) */
+int vq3d_preact_add_act_fwd(int32_t dtype, int64_t n, const void *x, const void *p, const float *a, const float *b,
+                            void *y, vq3d_stream_t stream);
+int vq3d_preact_add_act_bwd(int32_t dtype, int64_t n, const void *g, const void *x, const void *p, const float *a,
+                            void *gx, float *da, float *db, vq3d_stream_t stream);
+
 const char *vq3d_last_error(void);
 const char *vq3d_version(void);
 
